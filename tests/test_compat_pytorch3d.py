@@ -197,11 +197,10 @@ def test_ico_sphere_sampling_and_mesh_io(tmp_path):
     save_ply(ply, m.verts_packed(), m.faces_packed())
     v3, f3 = load_ply(ply)
     assert torch.allclose(v3, m.verts_packed(), atol=1e-5) and torch.equal(f3, m.faces_packed())
-    bunny = os.path.join("/root/reference/example_data/pointclouds/bunny-8000.ply")
-    if os.path.isfile(bunny):                                                             # binary little-endian PLY
-        vb, _ = load_ply(bunny)
-        z = np.load(os.path.join(ROOT, "tests", "golden", "clouds.npz"))
-        assert np.allclose(vb.numpy(), z["bunny_points"], atol=1e-6)
+    bunny = os.path.join(ROOT, "tests", "golden", "bunny-8000.ply")                     # binary little-endian PLY
+    vb, _ = load_ply(bunny)
+    z = np.load(os.path.join(ROOT, "tests", "golden", "clouds.npz"))
+    assert np.allclose(vb.numpy(), z["bunny_points"], atol=1e-6)
 
 
 def test_easydict_stand_in():

@@ -868,7 +868,7 @@ def test_bench_launches_its_own_ranks():
     env["BENCH_EXCHANGE"] = "overlap"   # (the three-collective form: "auto" would time both forms and keep the faster)
     env["BENCH_GRADIENT"] = "owner"     # (the form with the alpha-plane exchange; the default "auto" picks the bucket form at this size)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-12000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -891,6 +891,40 @@ def test_bench_launches_its_own_ranks():
                          env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True,
                          timeout=300)
     assert bad.returncode != 0 and "WORLD_SIZE" in (bad.stdout + bad.stderr)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_step_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): ONE JSON line with the headline keys,
+    exactly K timed steps, none of the --full figures; DIR holds the image and the two gradients of the last timed step,
+    which equal what the same step computes in this process."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out_dir = str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "3",
+                        "--dump-outputs", out_dir], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 30 and rec["config"]["timing"]["blocks_of_K_steps"] == 1 and rec["config"]["full"] is False
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["roofline"] is None
+    for k in ("cpu_baseline", "value_with_knn", "value_with_image_loss", "value_via_api"):
+        assert k not in rec, k
+    import bench
+    dev = torch.device("cuda:0")
+    wl = bench.Workload(dev, 1, bench.RowPartition(bench.S, 1, 0))
+    for name, want in zip(("image", "grad_points", "grad_colors"), wl.step()):
+        got = np.load(os.path.join(out_dir, name + ".npy"))
+        want = want.detach().cpu().numpy()
+        assert got.dtype == np.float32 and got.shape == want.shape, (name, got.dtype, got.shape, want.shape)
+        assert np.isfinite(got).all() and np.abs(got).max() > 0, name
+        err = np.abs(got - want).max() / np.abs(want).max()
+        assert err <= 1e-5, (name, err)
 
 
 def test_render_backward_multi_cloud_matches_unfused():

@@ -98,7 +98,7 @@ def test_bench_forced_dist_runs_the_rccl_path_on_one_gpu(exchange):
     env["BENCH_FORCE_DIST"] = "1"
     env["BENCH_EXCHANGE"] = exchange
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-traffic"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-traffic"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -29,7 +29,7 @@ for rnd in range(3):
             env[k] = v
         if lib != "default":
             env["DSS_HIP_LIBRARY"] = os.path.join(ROOT, lib)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--timed-only", "--no-cpu-baseline", "--no-traffic"] + extra,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--timed-only", "--full", "--no-cpu-baseline", "--no-traffic"] + extra,
                            env=env, capture_output=True, text=True, timeout=1200)
         line = [x for x in r.stdout.splitlines() if x.startswith("{")]
         if not line:

@@ -5,10 +5,10 @@ tag=${1:-r6}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 # (the counters measured by that very run; there is no committed fallback any more)
 cp gpurun_out/traffic_fine_kernel.json $out/traffic_fine_kernel.json 2>/dev/null
-rocprofv3 --kernel-trace --stats -d $out/ks -o b --output-format csv -- python bench.py --mode eager --no-cpu-baseline --no-traffic > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $out/ks -o b --output-format csv -- python bench.py --full --mode eager --no-cpu-baseline --no-traffic > /dev/null 2>&1
 cp $(find $out/ks -name '*kernel_stats.csv' | head -1) $out/kernel_stats.csv; rm -rf $out/ks
 python tools/step_timeline.py graph > $out/timeline.txt 2>&1
 # the causal multi-GPU step at world size 1 (RCCL path forced): its kernels and gaps
@@ -19,7 +19,7 @@ for c in cfg4 cfg5; do DSS_BENCH_MORTON=1 python tools/bench_large.py $c 2>/dev/
 for c in cfg4 cfg5; do
   # the driver's entry point, counters and rocprofv3 averages inside the line; the kernel statistics from the timed region
   # only (--timed-only: bench.py's own pair-counting torch kernels stay out of the trace)
-  python bench.py --workload $c --no-cpu-baseline > $out/bench_$c.json 2> $out/bench_$c.err
+  python bench.py --full --workload $c --no-cpu-baseline > $out/bench_$c.json 2> $out/bench_$c.err
   cp gpurun_out/traffic_fine_kernel_$c.json $out/traffic_fine_kernel_$c.json 2>/dev/null
   rocprofv3 --kernel-trace --stats -d $out/ks -o b --output-format csv -- python bench.py --workload $c --timed-only --mode eager --no-cpu-baseline --no-traffic > /dev/null 2>&1
   cp $(find $out/ks -name '*kernel_stats.csv' | head -1) $out/kernel_stats_$c.csv; rm -rf $out/ks
@@ -45,12 +45,12 @@ cp $(find $out/ks -name '*kernel_stats.csv' | head -1) $out/band_kernel_stats_cf
 for w in headline cfg3 cfg4 cfg5; do python tools/window_stats.py $w 2>/dev/null >> $out/backward_window_stats.jsonl; done
 { python tools/band_fused_timing.py 8 cyclic 3; TIMING_REBUILD=0 python tools/band_fused_timing.py 8 balanced 3; } > $out/band_gather_stamps.txt 2>&1
 python tools/setup_timing.py > $out/setup_timing.txt 2>&1
-for e in overlap auto; do BENCH_FORCE_DIST=1 BENCH_EXCHANGE=$e python bench.py --gpus 1 --no-cpu-baseline --no-traffic 2>/dev/null | grep '^{' > $out/bench_forced_dist_world1_$e.json; done
+for e in overlap auto; do BENCH_FORCE_DIST=1 BENCH_EXCHANGE=$e python bench.py --gpus 1 --full --no-cpu-baseline --no-traffic 2>/dev/null | grep '^{' > $out/bench_forced_dist_world1_$e.json; done
 python tools/knn_timing.py > $out/knn_timing.json 2>/dev/null
 python tools/knn_graph_timing.py > $out/knn_graph_timing.txt 2>/dev/null
 { python tools/knn_chain_timeline.py; python tools/knn_chain_timeline.py view; } > $out/knn_chain_timeline.txt 2>/dev/null
 for c in cfg2 cfg3 cfg4 cfg5; do python tools/gather_split.py $c >> $out/gather_split.jsonl 2>/dev/null; done
-BENCH_DIST_BACKEND=gloo python bench.py --gpus 2 --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_2ranks_gloo_one_gpu.json
+BENCH_DIST_BACKEND=gloo python bench.py --gpus 2 --full --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_2ranks_gloo_one_gpu.json
 # the clustered state of the reference's training loop (tests/golden/trained_cloud_cfg3.npz): kNN without / with the skip structure,
 # fine-pass phases, and the kernels of one step under the trace
 python tools/clustered_timing.py default@knn=3 default > $out/clustered_timing.txt 2>&1

@@ -32,7 +32,7 @@ def one_pass(counter):
     os.makedirs(d, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "eager", "--timed-only", "--steps", "16" if LARGE else "20",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "eager", "--timed-only", "--full", "--steps", "16" if LARGE else "20",
            "--warmup", "2" if LARGE else "5"] + WL_ARGS
     subprocess.run(cmd, cwd="/tmp", env=env, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     vals, other = [], []
@@ -57,7 +57,7 @@ def trace_pass():
     os.makedirs(d, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "eager" if LARGE else "graph", "--timed-only", "--steps",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "eager" if LARGE else "graph", "--timed-only", "--full", "--steps",
            "16" if LARGE else "100", "--warmup", "2" if LARGE else "10"] + WL_ARGS
     subprocess.run(cmd, cwd="/tmp", env=env, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     acc = {}

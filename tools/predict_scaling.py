@@ -59,10 +59,10 @@ out["per_rank_compute_us"] = {str(G): {k: {"max": v["graph_max_us"], "per_rank":
 multi1 = bands[1]["bands"]["graph_max_us"]
 floors = {}
 if which == "cfg2":
-    single = run([py, os.path.join(ROOT, "bench.py"), "--timed-only", "--no-cpu-baseline", "--no-traffic"])
+    single = run([py, os.path.join(ROOT, "bench.py"), "--timed-only", "--full", "--no-cpu-baseline", "--no-traffic"])
     single_us = single["ms_per_step"] * 1e3
     for form in ("overlap", "fold"):
-        f = run([py, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--timed-only", "--no-cpu-baseline", "--no-traffic"],
+        f = run([py, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--timed-only", "--full", "--no-cpu-baseline", "--no-traffic"],
                 {"BENCH_FORCE_DIST": "1", "BENCH_EXCHANGE": form})
         floors[form] = {"forced_world1_step_us": round(f["ms_per_step"] * 1e3, 2), "launch": f["launch"],
                         "collective_floor_us": round(max(f["ms_per_step"] * 1e3 - multi1, 0.0), 2)}

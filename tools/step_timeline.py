@@ -15,7 +15,7 @@ mode = sys.argv[1] if len(sys.argv) > 1 else "graph"
 import shutil
 shutil.rmtree(OUT, ignore_errors=True)   # (the traces of an earlier run in the same directory would be averaged in)
 subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", OUT, "--", sys.executable,
-                os.path.join(ROOT, "bench.py"), "--mode", mode, "--timed-only", "--steps", "100", "--warmup", "10"],
+                os.path.join(ROOT, "bench.py"), "--mode", mode, "--timed-only", "--full", "--steps", "100", "--warmup", "10"],
                cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 rows = []
 for f in glob.glob(os.path.join(OUT, "**", "*kernel_trace.csv"), recursive=True):
