@@ -32,9 +32,50 @@ int check_launch(const char *what)
 static std::atomic<int> g_opt[DSS_OPT_COUNT];
 int option(int which) { return (which >= 0 && which < DSS_OPT_COUNT) ? g_opt[which].load(std::memory_order_relaxed) : 0; }
 
-// Per-device cache of (CU count, resident workgroups per CU of the backward gather) -- see raster_backward.hip.
-static std::atomic<int> g_dev_cache[DSS_MAX_DEVICES][DSS_DEV_CACHE_SLOTS];
-std::atomic<int> *device_cache(int dev) { return (dev >= 0 && dev < DSS_MAX_DEVICES) ? g_dev_cache[dev] : nullptr; }
+// Per-device cache of the CU count and of the resident workgroups per CU of the kernels whose persistent grids are sized by
+// them (raster_backward.hip).  Lock-free: racing first callers compute and store the same values; a slot whose key is
+// claimed but whose value is not stored yet reads as a miss.  Devices beyond DSS_MAX_DEVICES and kernels beyond a full
+// table are queried on every call.
+#define DSS_MAX_DEVICES 64
+#define DSS_MAX_RESIDENT 64
+struct DeviceCache {
+    std::atomic<int> cus;
+    std::atomic<const void *> kernel[DSS_MAX_RESIDENT];
+    std::atomic<unsigned long long> value[DSS_MAX_RESIDENT];   // block << 32 | workgroups per CU; 0 = not stored yet
+};
+static DeviceCache g_dev[DSS_MAX_DEVICES];
+
+int cu_count(int dev)
+{
+    DeviceCache *dc = (dev >= 0 && dev < DSS_MAX_DEVICES) ? &g_dev[dev] : nullptr;
+    int cus = dc ? dc->cus.load(std::memory_order_relaxed) : 0;
+    if (cus == 0) {
+        hipDeviceProp_t prop;
+        cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
+        if (dc) dc->cus.store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
+unsigned resident_blocks(int dev, const void *kernel, int block)
+{
+    DeviceCache *dc = (dev >= 0 && dev < DSS_MAX_DEVICES) ? &g_dev[dev] : nullptr;
+    int i = 0;
+    for (; dc && i < DSS_MAX_RESIDENT; ++i) {
+        const void *k = dc->kernel[i].load(std::memory_order_acquire);
+        if (k == nullptr) break;
+        const unsigned long long v = dc->value[i].load(std::memory_order_acquire);
+        if (k == kernel && (v >> 32) == (unsigned)block) return (unsigned)v;
+    }
+    int per_cu = 0;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0);
+    (void)hipGetLastError();
+    if (per_cu < 1) per_cu = 1;
+    const void *expect = nullptr;
+    if (dc && i < DSS_MAX_RESIDENT && dc->kernel[i].compare_exchange_strong(expect, kernel, std::memory_order_acq_rel))
+        dc->value[i].store((unsigned long long)block << 32 | (unsigned)per_cu, std::memory_order_release);
+    return (unsigned)per_cu;
+}
 
 }  // namespace dss
 

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <atomic>
 #include "../../include/dss_hip.h"
 
 #define DSS_WAVE 64
@@ -128,9 +127,9 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 
 int check_launch(const char *what);
 int option(int which);                         // api.hip: value set by dss_set_option (0 = default)
-#define DSS_MAX_DEVICES 64
-#define DSS_DEV_CACHE_SLOTS 24
-std::atomic<int> *device_cache(int dev);       // api.hip: DSS_DEV_CACHE_SLOTS zero-initialised slots per device ordinal (nullptr beyond 64)
+int cu_count(int dev);                          // api.hip: compute units of device `dev` (cached per device)
+unsigned resident_blocks(int dev, const void *kernel, int block);   // api.hip: workgroups of `block` threads of `kernel`
+                                                                    // resident per CU, >= 1 (cached per device and kernel)
 
 // knn.hip: bbox (N,6) ordered ints = min xyz, max xyz of every cloud (NaN coordinates skipped)
 int launch_cloud_bbox(const float *points, const int64_t *first_idx, const int64_t *num_pts, int N, int64_t P, int *bbox,

@@ -2276,6 +2276,38 @@ static PrepLayout prep_layout(int N, int64_t P, int S, bool band = false)
     return L;
 }
 
+// Workspace of the long-list path (P > PREP_MAX_POINTS), relative to its base: the median histograms and visible counters
+// (zeroed together), the visible list, rs, the dense alpha-gradient plane and the counting sort of the list by screen cell.
+struct LongLayout {
+    size_t hist, vis_count, vis_list, rs, alpha, cell_of, sorted, cell_start, cell_total, block_hist, bytes;
+};
+static LongLayout long_layout(int N, int64_t P, int S)
+{
+    LongLayout L;
+    const size_t n = N > 0 ? N : 1, s = S > 0 ? S : 1, p = P > 0 ? (size_t)P : 1;
+    const size_t cells = (size_t)make_cells(N > 0 ? N : 1, S > 0 ? S : 1).total;
+    size_t off = 0;
+    L.hist = off;       L.vis_count = off + 3 * n * MED_BINS * 4;   // histograms, then the list lengths (unsorted, sorted)
+    off += align_up(3 * n * MED_BINS * 4 + 256, 256);
+    L.vis_list = off;   off += align_up(p * 4, 256);                 // compacted visible list
+    L.rs = off;         off += align_up(n * 4, 256);
+    L.alpha = off;      off += align_up(n * s * s * 4, 256);         // dense alpha-gradient plane
+    L.cell_of = off;    off += align_up(p * 4, 256);                 // cell of every list entry
+    L.sorted = off;     off += align_up(p * 4, 256);                 // cell-ordered list
+    L.cell_start = off; off += align_up(cells * 4, 256);             // first list position of every cell
+    L.cell_total = off; off += align_up(cells * 4, 256);             // entries per cell
+    L.block_hist = off; off += align_up(cell_blocks(P) * cells * 4, 256);   // per sort block: entries of every cell in earlier blocks
+    L.bytes = off;
+    return L;
+}
+
+// The PER instantiations of the preparation kernels (points per thread: 2 or 4 for the compaction and the band filter,
+// 1 .. 16 for fb_prep_kernel, indexed by log2)
+static const decltype(&backward_compact_kernel<2>) compact_by_per[] = {backward_compact_kernel<2>, backward_compact_kernel<4>};
+static const decltype(&band_filter_kernel<2>) band_filter_by_per[] = {band_filter_kernel<2>, band_filter_kernel<4>};
+static const decltype(&fb_prep_kernel<1>) fb_prep_by_per[] = {fb_prep_kernel<1>, fb_prep_kernel<2>, fb_prep_kernel<4>,
+                                                              fb_prep_kernel<8>, fb_prep_kernel<16>};
+
 static void launch_prep(const float *radii, const uint8_t *visible, const int64_t *first_idx, const int64_t *num_pts,
                         int N, int64_t P, float radii_s, float *rs, char *w, const PrepLayout &L, float *grad_pts,
                         float *grad_feat, int C, const float *grad_out, size_t npix, hipStream_t st)
@@ -2287,13 +2319,9 @@ static void launch_prep(const float *radii, const uint8_t *visible, const int64_
     uint2 *vis_keys = reinterpret_cast<uint2 *>(w + L.vis_keys);
     uint32_t *chunk_hist = reinterpret_cast<uint32_t *>(w + L.chunk_hist);
     uint2 *seg_range = reinterpret_cast<uint2 *>(w + L.seg_range);
-#define DSS_LAUNCH_COMPACT(PER_)                                                                                       \
-    hipLaunchKernelGGL(backward_compact_kernel<PER_>, dim3(L.chunks + alpha_wgs), dim3(PREP_THREADS), 0, st, radii,       \
-                       visible, first_idx, num_pts, N, P, L.chunks, seg_count, vis_list, vis_keys, chunk_hist, seg_range, \
-                       grad_pts, grad_feat, C, grad_out, alpha, npix)
-    if (L.per == 2) DSS_LAUNCH_COMPACT(2);
-    else DSS_LAUNCH_COMPACT(4);
-#undef DSS_LAUNCH_COMPACT
+    hipLaunchKernelGGL(compact_by_per[L.per == 2 ? 0 : 1], dim3(L.chunks + alpha_wgs), dim3(PREP_THREADS), 0, st, radii,
+                       visible, first_idx, num_pts, N, P, L.chunks, seg_count, vis_list, vis_keys, chunk_hist, seg_range,
+                       grad_pts, grad_feat, C, grad_out, alpha, npix);
     hipLaunchKernelGGL(median_visible_kernel, dim3(N), dim3(PREP_THREADS), 0, st, first_idx, num_pts, P, L.chunks,
                        L.per * PREP_THREADS, seg_range, vis_keys, chunk_hist, radii_s, rs);
 }
@@ -2451,19 +2479,49 @@ extern "C" int dss_splat_backward(const float *points, const float *radii, const
 
 extern "C" size_t dss_render_backward_workspace(int N, int64_t P, int S)
 {
-    const size_t n = N > 0 ? N : 1, s = S > 0 ? S : 1;
     if (P <= PREP_MAX_POINTS) return prep_layout(N, P, S).bytes;
-    const size_t cells = (size_t)make_cells(N > 0 ? N : 1, S > 0 ? S : 1).total;
-    const size_t p1 = (size_t)(P > 0 ? P : 1);
-    return align_up((size_t)3 * n * MED_BINS * 4 + 256, 256)  // histograms + visible counter
-           + align_up(p1 * 4, 256)                            // compacted visible list
-           + align_up(n * 4, 256)                             // rs
-           + align_up(n * s * s * 4, 256)                     // dense alpha-gradient plane
-           + 2 * align_up(p1 * 4, 256)                        // cell of every list entry, cell-ordered list
-           + 2 * align_up(cells * 4, 256)                     // entries per cell, first list position of every cell
-           + align_up(cell_blocks(P) * cells * 4, 256);       // per sort block: entries of every cell in earlier blocks
+    return long_layout(N, P, S).bytes;
 }
 
+// One instantiation of render_backward_kernel<C, SEG, TPW, A32, CYC, PREP, BAND> as data: RGB (C = 3) or generic features
+// (C = 0), segmented short list or cell-sorted long list, tasks per wavefront, 32-bit offsets, tile-row-cyclic band,
+// preparation stages inside the launch, band filter inside the launch.
+struct GatherVariant {
+    bool c3, seg;
+    int tpw;
+    bool a32, cyc, prep, band;
+};
+using GatherKernel = decltype(&render_backward_kernel<3, true, 4, true>);
+
+template <int C, bool SEG, bool CYC, bool PREP, bool BAND>
+static GatherKernel gather_by_tpw(int tpw)
+{
+    return tpw == 4 ? render_backward_kernel<C, SEG, 4, true, CYC, PREP, BAND>
+                    : (tpw == 2 ? render_backward_kernel<C, SEG, 2, true, CYC, PREP, BAND> : render_backward_kernel<C, SEG, 1, true, CYC, PREP, BAND>);
+}
+
+// The instantiations that exist, and no others (nullptr for any other combination):
+//   whole image or contiguous band:       <C, SEG, 1|2|4, true>, and <C, SEG, 4, false> (64-bit offsets)
+//   tile-row-cyclic band (RGB, 32-bit):   <3, SEG, 1|2|4, true, true>
+//   preparation inside the launch:        <C, true, 1|2|4, true, false, true>
+//   band filter inside the launch:        <C, true, 1|2|4, true, false, true, true>, <3, true, 1|2|4, true, true, true, true>
+static GatherKernel gather_kernel(const GatherVariant &v)
+{
+    if ((v.cyc && !v.c3) || (!v.a32 && (v.cyc || v.prep || v.band)) || (!v.seg && v.prep) || (v.band && !v.prep)) return nullptr;
+    if (v.band)
+        return v.cyc ? gather_by_tpw<3, true, true, true, true>(v.tpw)
+                     : (v.c3 ? gather_by_tpw<3, true, false, true, true>(v.tpw) : gather_by_tpw<0, true, false, true, true>(v.tpw));
+    if (v.prep) return v.c3 ? gather_by_tpw<3, true, false, true, false>(v.tpw) : gather_by_tpw<0, true, false, true, false>(v.tpw);
+    if (v.cyc) return v.seg ? gather_by_tpw<3, true, true, false, false>(v.tpw) : gather_by_tpw<3, false, true, false, false>(v.tpw);
+    if (!v.a32)
+        return v.c3 ? (v.seg ? render_backward_kernel<3, true, 4, false> : render_backward_kernel<3, false, 4, false>)
+                    : (v.seg ? render_backward_kernel<0, true, 4, false> : render_backward_kernel<0, false, 4, false>);
+    return v.c3 ? (v.seg ? gather_by_tpw<3, true, false, false, false>(v.tpw) : gather_by_tpw<3, false, false, false, false>(v.tpw))
+                : (v.seg ? gather_by_tpw<0, true, false, false, false>(v.tpw) : gather_by_tpw<0, false, false, false, false>(v.tpw));
+}
+
+// Stages: validate -> choose the path (short or long list, fused or round-3 preparation, band variant, tasks per wavefront,
+// addressing) -> carve the workspace and launch the preparation -> the gather launch.
 static int render_backward_impl(bool run_prep, const float *grad_out, const int32_t *idx, const float *qvalue, const float *wsum,
                                 const float *scaler, const float *points, const float *radii,
                                 const uint8_t *visible, const int64_t *first_idx, const int64_t *num_pts, int N,
@@ -2473,6 +2531,7 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
                                 const float *grad_full = nullptr /* (N,S,S,C+1): owner mode of a row band, see OwnArgs */,
                                 const float *occ_full = nullptr /* (N,S,S) dense: owner mode fed by the all-gathered alpha-gradient plane */)
 {
+    // ---- validate
     if (N <= 0 || P < 0 || S <= 0 || K <= 0 || C < 1 || C > BLEND_MAX_C || row0 < 0 || row1 > S || row0 >= row1 ||
         row_cycle < 1 || (row_cycle & (row_cycle - 1)) || row_cycle > 4096) {
         set_error("dss_render_backward: bad sizes N=%d P=%lld S=%d K=%d C=%d rows=[%d,%d) cycle %d", N, (long long)P, S, K, C,
@@ -2508,45 +2567,31 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
         set_error("dss_render_backward: workspace %zu bytes < required %zu", workspace_bytes, need);
         return DSS_ERR_WORKSPACE;
     }
+    if (((uintptr_t)grad_out & 15u) && C == 3) { set_error("dss_render_backward: grad_out must be 16-byte aligned"); return DSS_ERR_INVALID_ARGUMENT; }
+
+    // ---- choose the path
     hipStream_t st = as_stream(stream);
     char *w = reinterpret_cast<char *>(workspace);
     const bool small = P <= PREP_MAX_POINTS;
-    int n_seg = 0, seg_pts = 0;
-    uint32_t *vis_count;  // small: PREP_MAX_SEG per-segment counters; otherwise one global counter
-    int32_t *vis_list;
-    float *rs;
     const size_t npix = (size_t)N * rows * S;
-    const float *alpha;
-    if (((uintptr_t)grad_out & 15u) && C == 3) { set_error("dss_render_backward: grad_out must be 16-byte aligned"); return DSS_ERR_INVALID_ARGUMENT; }
-    // persistent grid = exactly the resident capacity of the chip for this kernel (a larger grid would
-    // leave late workgroups waiting for slots while their share of the list sits idle)
-    // Cached per DEVICE ordinal (api.hip: four atomic slots per device -- CU count, capacity for C == 3, capacity for the
-    // generic-channel kernel): sized by the <C, true, 4, true> instantiation, the variant with the most registers, so the
-    // grid never exceeds the resident capacity of whichever variant is launched below.  Racing first callers compute and
-    // store the same values.
     int dev = 0;
     (void)hipGetDevice(&dev);
-    std::atomic<int> *dc = device_cache(dev);
-    int n_cus = dc ? dc[0].load(std::memory_order_relaxed) : 0;
-    int cap = dc ? dc[C == 3 ? 1 : 2].load(std::memory_order_relaxed) : 0;
-    if (cap == 0 || n_cus == 0) {
-        int cus = 256, per_cu = 4;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (C == 3)
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_backward_kernel<3, true, 4, true>, 256, 0);
-        else
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_backward_kernel<0, true, 4, true>, 256, 0);
-        if (per_cu < 1) per_cu = 1;
-        n_cus = cus;
-        cap = cus * per_cu;
-        (void)hipGetLastError();
-        if (dc) {
-            dc[0].store(n_cus, std::memory_order_relaxed);
-            dc[C == 3 ? 1 : 2].store(cap, std::memory_order_relaxed);
-        }
-    }
+    const int n_cus = cu_count(dev);
+    // The persistent grid of every gather launch is at most pgrid: one workgroup per four list entries, capped by the resident
+    // capacity of the reference variant <C, true, 4, true>.  A workgroup that is not resident at launch would start its share
+    // when the others end theirs, so a launch is also clamped to what ITS instantiation keeps resident:
+    //   round-3 and cyclic launches:                             min(pgrid, resident(own))
+    //   preparation inside the launch (fused with PREP, BAND):   max(min(pgrid, resident(own)), N + 8)  (the first N
+    //                                                            workgroups select the medians the others wait for)
+    //   fused launch without PREP (gather stage alone, form 5):  pgrid
+    // with resident(v) = n_cus x the workgroups of v resident per CU.
+    const unsigned cap = (unsigned)n_cus * resident_blocks(dev, (const void *)gather_kernel({C == 3, true, 4, true, false, false, false}), 256);
     const unsigned pgrid = (unsigned)((P + 3) / 4 < cap ? (P + 3) / 4 : cap);
+    auto gather_grid = [&](const GatherVariant &v, bool fused_launch) -> unsigned {
+        if (fused_launch && !v.prep) return pgrid;
+        const unsigned g = std::min(pgrid, (unsigned)n_cus * resident_blocks(dev, (const void *)gather_kernel(v), 256));
+        return v.prep ? std::max(g, (unsigned)N + 8u) : g;
+    };
     const uint32_t large_waves = 6u * (uint32_t)n_cus * 4u;
     // tasks per wavefront: four when the list is long enough to keep every resident wavefront busy with whole groups
     // (throughput-bound), fewer -- more lanes per task, shorter dependent chains -- for short lists.  The visible count is
@@ -2565,93 +2610,70 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
     if (!a32) tpw = 4;
     if (!a32 && world) { set_error("dss_render_backward: the fused projection needs gathered tensors below 4 GB"); return DSS_ERR_UNSUPPORTED; }
     // Round-4 preparation of short lists (fb_prep_kernel / fb_median): whole image, 32-bit offsets, at most 64 clouds.
-    // DSS_OPT_BACKWARD_FUSED: 0 = automatic, 1 = the round-3 launch sequence, 4 = two launches (segments + alpha plane |
-    // medians + gather), 5 = three (segments + alpha plane | medians | gather).
+    // DSS_OPT_BACKWARD_FUSED: 0 = automatic, 4 = two launches (segments + alpha plane | medians + gather), 5 = three
+    // (segments + alpha plane | medians | gather), any other value = the round-3 launch sequence.
     int fused_opt = option(DSS_OPT_BACKWARD_FUSED);
     if (fused_opt == 0) fused_opt = DSS_BACKWARD_FUSED_DEFAULT;
-    // grid of a BAND variant (below): the resident capacity of the instantiation, cached per device in slots 10.. of the cache
-    auto band_grid = [&](int tpw_) -> unsigned {
-        const int slot = 10 + (C == 3 ? (cyc ? 3 : 0) : 6) + (tpw_ == 4 ? 2 : (tpw_ == 2 ? 1 : 0));
-        int fcap = (dc && slot < DSS_DEV_CACHE_SLOTS) ? dc[slot].load(std::memory_order_relaxed) : 0;
-        if (fcap == 0) {
-            int per_cu = 0;
-#define DSS_OCC_B(CC, TT, YY) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_backward_kernel<CC, true, TT, true, YY, true, true>, 256, 0)
-            if (C == 3 && cyc) { if (tpw_ == 4) DSS_OCC_B(3, 4, true); else if (tpw_ == 2) DSS_OCC_B(3, 2, true); else DSS_OCC_B(3, 1, true); }
-            else if (C == 3) { if (tpw_ == 4) DSS_OCC_B(3, 4, false); else if (tpw_ == 2) DSS_OCC_B(3, 2, false); else DSS_OCC_B(3, 1, false); }
-            else { if (tpw_ == 4) DSS_OCC_B(0, 4, false); else if (tpw_ == 2) DSS_OCC_B(0, 2, false); else DSS_OCC_B(0, 1, false); }
-#undef DSS_OCC_B
-            (void)hipGetLastError();
-            fcap = n_cus * (per_cu > 0 ? per_cu : 1);
-            if (dc && slot < DSS_DEV_CACHE_SLOTS) dc[slot].store(fcap, std::memory_order_relaxed);
-        }
-        unsigned g = pgrid;
-        if ((unsigned)fcap < g) g = (unsigned)fcap;
-        if (g < (unsigned)N + 8u) g = (unsigned)N + 8u;
-        return g;
-    };
-    FusedPrep FP = FusedPrep();
-    const int astride = 1;
-    bool fused = false, band = false;
-    if (small) {
-        band = rows < S || cyc;
-        const PrepLayout L = prep_layout(N, P, S, band);
-        // row band (multi-GPU): the two-launch form with the band filter inside the gather launch (BAND variants: fused_opt 4,
-        // RGB or generic features on a contiguous band, RGB on a tile-row-cyclic one, every worker workgroup's share of the
-        // list within BAND_SHARE entries); anything else takes the round-3 sequence
-        fused = (fused_opt == 4 || fused_opt == 5) && a32 && N <= 64 && (unsigned)N + 8u <= pgrid &&
-                (!band || (fused_opt == 4 && (!cyc || C == 3) && world == nullptr));
-        if (fused && fused_opt == 4 && !(tpw_opt == 1 || tpw_opt == 2 || tpw_opt == 4)) {
-            // two-phase gather with its groups dealt per workgroup: two tasks per wavefront win as soon as there is about a
-            // task per resident wavefront (32,684 points @512^2: 58.7 us per step against 60.5 with one, 59.3 with four)
-            // (a band keeps about (rows + two search radii) / S of the visible points: estimated as 2 rows / S)
-            const long long est = band ? est_tasks * 2 * rows / S : est_tasks;
-            tpw = est >= 16ll * cap * 4 ? 4 : (est >= 1ll * cap * 4 ? 2 : 1);
-            // a tile-row-cyclic band owns at most eight consecutive rows of any window: many small tasks, one lane row each
-            // (8 ranks x 32,684 points: 101-105 us per rank and step with four tasks per wavefront, 110-114 with two)
-            if (cyc) tpw = 4;
-        }
-        // (every worker workgroup of a BAND launch holds its share of the list in LDS)
-        if (fused && band && (long long)BAND_SHARE * ((long long)band_grid(tpw) - N) < (long long)P) fused = false;
-        if (fused) {
-            n_seg = L.f_chunks;
-            seg_pts = L.f_per * FB_THREADS;
-            vis_count = reinterpret_cast<uint32_t *>(w + L.seg_count);
-            vis_list = reinterpret_cast<int32_t *>(w + L.vis_list);
-            rs = rs_out ? rs_out : reinterpret_cast<float *>(w + L.rs);
-            FP.visible = visible; FP.seg_count = vis_count; FP.vis_list = vis_list;
-            FP.keys = reinterpret_cast<uint32_t *>(w + L.vis_keys);
-            FP.chunk_hist = reinterpret_cast<uint32_t *>(w + L.chunk_hist);
-            FP.seg_range = reinterpret_cast<uint2 *>(w + L.seg_range);
-            FP.tags = reinterpret_cast<unsigned long long *>(w + L.tags);
-            FP.rs = rs; FP.P = P;
-            FP.chunks = L.f_chunks; FP.per = L.f_per; FP.radii_s = radii_s;
-            float *plane = reinterpret_cast<float *>(w + L.alpha);
-            alpha = plane;
-            // owner mode: the dense plane holds the alpha channel of the FULL image gradient (the medians run inside the next
-            // launch, so the rows an owned window can reach are not known yet; the blend half does not read the plane)
-            const float *plane_src = own ? grad_full : grad_out;
-            const size_t plane_px = own_given ? (size_t)0 : (own ? (size_t)N * S * S : npix);
-            if (own && !own_given) { OW.alpha = plane; OW.astride = 1; }
-            if (run_prep) {
-                // stage 1: one workgroup per segment + the dense alpha plane in extra workgroups
-                const unsigned alpha_wgs = (unsigned)((plane_px + FB_ALPHA_PER_WG - 1) / FB_ALPHA_PER_WG);
-#define DSS_LAUNCH_FB_PREP(PER_)                                                                                          \
-    hipLaunchKernelGGL(fb_prep_kernel<PER_>, dim3((unsigned)L.f_chunks + alpha_wgs), dim3(FB_THREADS), 0, st, FP, radii,   \
-                       first_idx, num_pts, N, grad_pts, grad_feat, C, plane_src, plane, plane_px)
-                switch (L.f_per) {
-                    case 1: DSS_LAUNCH_FB_PREP(1); break;
-                    case 2: DSS_LAUNCH_FB_PREP(2); break;
-                    case 4: DSS_LAUNCH_FB_PREP(4); break;
-                    case 8: DSS_LAUNCH_FB_PREP(8); break;
-                    default: DSS_LAUNCH_FB_PREP(16); break;
-                }
-#undef DSS_LAUNCH_FB_PREP
-                if (fused_opt == 5)
-                    hipLaunchKernelGGL(fb_median_kernel, dim3((unsigned)N), dim3(FB_THREADS), 0, st, FP, first_idx, num_pts);
-            }
-        }
+    // row band (multi-GPU): the two-launch form with the band filter inside the gather launch (BAND variants: fused_opt 4,
+    // RGB or generic features on a contiguous band, RGB on a tile-row-cyclic one, every worker workgroup's share of the
+    // list within BAND_SHARE entries); anything else takes the round-3 sequence
+    const bool band = rows < S || cyc;
+    bool fused = small && (fused_opt == 4 || fused_opt == 5) && a32 && N <= 64 && (unsigned)N + 8u <= pgrid &&
+                 (!band || (fused_opt == 4 && (!cyc || C == 3) && world == nullptr));
+    if (fused && fused_opt == 4 && !(tpw_opt == 1 || tpw_opt == 2 || tpw_opt == 4)) {
+        // two-phase gather with its groups dealt per workgroup: two tasks per wavefront win as soon as there is about a
+        // task per resident wavefront (32,684 points @512^2: 58.7 us per step against 60.5 with one, 59.3 with four)
+        // (a band keeps about (rows + two search radii) / S of the visible points: estimated as 2 rows / S)
+        const long long est = band ? est_tasks * 2 * rows / S : est_tasks;
+        tpw = est >= 16ll * cap * 4 ? 4 : (est >= 1ll * cap * 4 ? 2 : 1);
+        // a tile-row-cyclic band owns at most eight consecutive rows of any window: many small tasks, one lane row each
+        // (8 ranks x 32,684 points: 101-105 us per rank and step with four tasks per wavefront, 110-114 with two)
+        if (cyc) tpw = 4;
     }
-    if (small && !fused) {
+    // BAND variants: medians always inside the launch (run_prep false only skips the segment launch: the keys of the
+    // preceding full call are still in the workspace)
+    GatherVariant v = {C == 3, small, tpw, a32, cyc, fused && (band || (run_prep && fused_opt != 5)), fused && band};
+    // (every worker workgroup of a BAND launch holds its share of the list in LDS)
+    if (v.band && (long long)BAND_SHARE * ((long long)gather_grid(v, true) - N) < (long long)P) fused = v.prep = v.band = false;
+
+    // ---- carve the workspace, launch the preparation (run_prep false: the gather stage alone, on what a preceding full
+    // call left in the workspace)
+    int n_seg = 0, seg_pts = 0;
+    uint32_t *vis_count;  // short lists: per-segment counters; long lists: the visible and the sorted list length
+    int32_t *vis_list;
+    float *rs;
+    const float *alpha;
+    FusedPrep FP = FusedPrep();
+    if (fused) {
+        const PrepLayout L = prep_layout(N, P, S, band);
+        n_seg = L.f_chunks;
+        seg_pts = L.f_per * FB_THREADS;
+        vis_count = reinterpret_cast<uint32_t *>(w + L.seg_count);
+        vis_list = reinterpret_cast<int32_t *>(w + L.vis_list);
+        rs = rs_out ? rs_out : reinterpret_cast<float *>(w + L.rs);
+        FP.visible = visible; FP.seg_count = vis_count; FP.vis_list = vis_list;
+        FP.keys = reinterpret_cast<uint32_t *>(w + L.vis_keys);
+        FP.chunk_hist = reinterpret_cast<uint32_t *>(w + L.chunk_hist);
+        FP.seg_range = reinterpret_cast<uint2 *>(w + L.seg_range);
+        FP.tags = reinterpret_cast<unsigned long long *>(w + L.tags);
+        FP.rs = rs; FP.P = P;
+        FP.chunks = L.f_chunks; FP.per = L.f_per; FP.radii_s = radii_s;
+        float *plane = reinterpret_cast<float *>(w + L.alpha);
+        alpha = plane;
+        // owner mode: the dense plane holds the alpha channel of the FULL image gradient (the medians run inside the next
+        // launch, so the rows an owned window can reach are not known yet; the blend half does not read the plane)
+        const float *plane_src = own ? grad_full : grad_out;
+        const size_t plane_px = own_given ? (size_t)0 : (own ? (size_t)N * S * S : npix);
+        if (own && !own_given) { OW.alpha = plane; OW.astride = 1; }
+        if (run_prep) {
+            // stage 1: one workgroup per segment + the dense alpha plane in extra workgroups
+            const unsigned alpha_wgs = (unsigned)((plane_px + FB_ALPHA_PER_WG - 1) / FB_ALPHA_PER_WG);
+            hipLaunchKernelGGL(fb_prep_by_per[__builtin_ctz(L.f_per)], dim3((unsigned)L.f_chunks + alpha_wgs), dim3(FB_THREADS), 0,
+                               st, FP, radii, first_idx, num_pts, N, grad_pts, grad_feat, C, plane_src, plane, plane_px);
+            if (fused_opt == 5)
+                hipLaunchKernelGGL(fb_median_kernel, dim3((unsigned)N), dim3(FB_THREADS), 0, st, FP, first_idx, num_pts);
+        }
+    } else if (small) {
         const PrepLayout L = prep_layout(N, P, S);
         n_seg = L.chunks;
         seg_pts = L.per * PREP_THREADS;
@@ -2661,175 +2683,66 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
         rs = rs_out ? rs_out : reinterpret_cast<float *>(w + L.rs);
         if (run_prep)
             launch_prep(radii, visible, first_idx, num_pts, N, P, radii_s, rs, w, L, grad_pts, grad_feat, C, grad_out, npix, st);
-        if (run_prep && rows < S) {  // row band: keep only the points that can reach it
-            if (L.per == 2)
-                hipLaunchKernelGGL(band_filter_kernel<2>, dim3(L.chunks), dim3(PREP_THREADS), 0, st, points, radii, rs,
-                                   first_idx, num_pts, N, S, row0, rows, vis_count, vis_list, grad_pts, grad_feat, C, tshift, own);
-            else
-                hipLaunchKernelGGL(band_filter_kernel<4>, dim3(L.chunks), dim3(PREP_THREADS), 0, st, points, radii, rs,
-                                   first_idx, num_pts, N, S, row0, rows, vis_count, vis_list, grad_pts, grad_feat, C, tshift, own);
-        }
-    } else if (!small) {
-        const size_t hist_bytes = (size_t)3 * N * MED_BINS * 4;
+        if (run_prep && rows < S)  // row band: keep only the points that can reach it
+            hipLaunchKernelGGL(band_filter_by_per[L.per == 2 ? 0 : 1], dim3(L.chunks), dim3(PREP_THREADS), 0, st, points, radii,
+                               rs, first_idx, num_pts, N, S, row0, rows, vis_count, vis_list, grad_pts, grad_feat, C, tshift, own);
+    } else {
+        const LongLayout L = long_layout(N, P, S);
         const CellGrid cg = make_cells(N, S);
-        uint32_t *hist = reinterpret_cast<uint32_t *>(w);
-        vis_count = reinterpret_cast<uint32_t *>(w + hist_bytes);
-        size_t off = align_up(hist_bytes + 256, 256);
-        vis_list = reinterpret_cast<int32_t *>(w + off);
-        off += align_up((size_t)P * 4, 256);
-        rs = rs_out ? rs_out : reinterpret_cast<float *>(w + off);
-        off += align_up((size_t)N * 4, 256);
-        float *plane = reinterpret_cast<float *>(w + off);
+        uint32_t *hist = reinterpret_cast<uint32_t *>(w + L.hist);
+        vis_count = reinterpret_cast<uint32_t *>(w + L.vis_count);
+        int32_t *unsorted = reinterpret_cast<int32_t *>(w + L.vis_list);
+        rs = rs_out ? rs_out : reinterpret_cast<float *>(w + L.rs);
+        float *plane = reinterpret_cast<float *>(w + L.alpha);
         alpha = plane;
-        off += align_up((size_t)N * S * S * 4, 256);
-        uint32_t *cell_of = reinterpret_cast<uint32_t *>(w + off);
-        off += align_up((size_t)P * 4, 256);
-        int32_t *sorted = reinterpret_cast<int32_t *>(w + off);
-        off += align_up((size_t)P * 4, 256);
-        uint32_t *cell_start = reinterpret_cast<uint32_t *>(w + off);
-        off += align_up((size_t)cg.total * 4, 256);
-        uint32_t *cell_total = reinterpret_cast<uint32_t *>(w + off);
-        off += align_up((size_t)cg.total * 4, 256);
-        uint32_t *block_hist = reinterpret_cast<uint32_t *>(w + off);
-        int32_t *unsorted = vis_list;
+        uint32_t *cell_of = reinterpret_cast<uint32_t *>(w + L.cell_of);
+        int32_t *sorted = reinterpret_cast<int32_t *>(w + L.sorted);
+        uint32_t *cell_start = reinterpret_cast<uint32_t *>(w + L.cell_start);
+        uint32_t *cell_total = reinterpret_cast<uint32_t *>(w + L.cell_total);
+        uint32_t *block_hist = reinterpret_cast<uint32_t *>(w + L.block_hist);
         vis_list = sorted;
-
         if (run_prep) {
-        if (!own)
-            hipLaunchKernelGGL(alpha_plane_kernel, dim3((unsigned)((npix + ALPHA_PIX_PER_WG - 1) / ALPHA_PIX_PER_WG)), dim3(1024),
-                               0, st, grad_out, plane, npix, C);
-        if (hipMemsetAsync(hist, 0, hist_bytes + 256, st) != hipSuccess) return check_launch("memset render_backward");
-        const unsigned blocks = (unsigned)((P + MED_PTS_PER_WG - 1) / MED_PTS_PER_WG);
-        hipLaunchKernelGGL(visible_scan_kernel, dim3(blocks), dim3(MED_THREADS), 0, st, radii, visible, first_idx,
-                           num_pts, N, P, hist, vis_count, unsorted, grad_pts, grad_feat, C, (rows < S || cyc) ? 1 : 0);
-        hipLaunchKernelGGL(median_hist_kernel<1>, dim3(blocks), dim3(MED_THREADS), 0, st, radii, visible, first_idx,
-                           num_pts, N, P, hist);
-        hipLaunchKernelGGL(median_hist_kernel<2>, dim3(blocks), dim3(MED_THREADS), 0, st, radii, visible, first_idx,
-                           num_pts, N, P, hist);
-        hipLaunchKernelGGL(median_final_kernel, dim3(N), dim3(MED_THREADS), 0, st, hist, N, radii_s, rs);
-        if (own && !own_given)   // (the band's own plane above is not read in owner mode: its region holds the full-layout one)
-            hipLaunchKernelGGL(alpha_rows_kernel, dim3((unsigned)S, (unsigned)N), dim3(256), 0, st, grad_full, plane, rs, N, S, C,
-                               row0, rows, tshift);
-        const unsigned cb = (unsigned)cell_blocks(P);   // (the visible count is only known on the device: P bounds it)
-        const size_t lds = (size_t)cg.total * 4;
-        const bool band_l = rows < S || cyc;   // row band: the entries that cannot reach it drop out of the sorted list
-        hipLaunchKernelGGL(cell_hist_kernel, dim3(cb), dim3(CELL_THREADS), lds, st, points, first_idx, num_pts, N, S, cg,
-                           vis_count, unsorted, cell_of, block_hist, band_l ? radii : nullptr, rs, row0, rows, tshift, own);
-        hipLaunchKernelGGL(cell_block_scan_kernel, dim3((unsigned)((cg.total + 255) / 256)), dim3(256), 0, st, vis_count,
-                           cg.total, block_hist, cell_total);
-        hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, cell_total, cell_start, cg.total, vis_count + 1);
-        hipLaunchKernelGGL(cell_scatter_kernel, dim3(cb), dim3(CELL_THREADS), lds, st, cg, vis_count, unsorted, cell_of,
-                           cell_start, block_hist, sorted);
+            if (!own)
+                hipLaunchKernelGGL(alpha_plane_kernel, dim3((unsigned)((npix + ALPHA_PIX_PER_WG - 1) / ALPHA_PIX_PER_WG)), dim3(1024),
+                                   0, st, grad_out, plane, npix, C);
+            if (hipMemsetAsync(hist, 0, L.vis_list - L.hist, st) != hipSuccess) return check_launch("memset render_backward");
+            const unsigned blocks = (unsigned)((P + MED_PTS_PER_WG - 1) / MED_PTS_PER_WG);
+            hipLaunchKernelGGL(visible_scan_kernel, dim3(blocks), dim3(MED_THREADS), 0, st, radii, visible, first_idx,
+                               num_pts, N, P, hist, vis_count, unsorted, grad_pts, grad_feat, C, band ? 1 : 0);
+            hipLaunchKernelGGL(median_hist_kernel<1>, dim3(blocks), dim3(MED_THREADS), 0, st, radii, visible, first_idx,
+                               num_pts, N, P, hist);
+            hipLaunchKernelGGL(median_hist_kernel<2>, dim3(blocks), dim3(MED_THREADS), 0, st, radii, visible, first_idx,
+                               num_pts, N, P, hist);
+            hipLaunchKernelGGL(median_final_kernel, dim3(N), dim3(MED_THREADS), 0, st, hist, N, radii_s, rs);
+            if (own && !own_given)   // (the band's own plane above is not read in owner mode: its region holds the full-layout one)
+                hipLaunchKernelGGL(alpha_rows_kernel, dim3((unsigned)S, (unsigned)N), dim3(256), 0, st, grad_full, plane, rs, N, S, C,
+                                   row0, rows, tshift);
+            const unsigned cb = (unsigned)cell_blocks(P);   // (the visible count is only known on the device: P bounds it)
+            const size_t lds = (size_t)cg.total * 4;
+            // (row band: the entries that cannot reach it drop out of the sorted list)
+            hipLaunchKernelGGL(cell_hist_kernel, dim3(cb), dim3(CELL_THREADS), lds, st, points, first_idx, num_pts, N, S, cg,
+                               vis_count, unsorted, cell_of, block_hist, band ? radii : nullptr, rs, row0, rows, tshift, own);
+            hipLaunchKernelGGL(cell_block_scan_kernel, dim3((unsigned)((cg.total + 255) / 256)), dim3(256), 0, st, vis_count,
+                               cg.total, block_hist, cell_total);
+            hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, cell_total, cell_start, cg.total, vis_count + 1);
+            hipLaunchKernelGGL(cell_scatter_kernel, dim3(cb), dim3(CELL_THREADS), lds, st, cg, vis_count, unsorted, cell_of,
+                               cell_start, block_hist, sorted);
         }
         if (own && !own_given) { OW.alpha = plane; OW.astride = 1; }
         vis_count += 1;   // the gather walks the SORTED list: its length (written by cell_scan_kernel) is the second word
     }
-    if (fused) {
-        // the gather launch, with the preparation stages the mode puts inside it (run_prep false: the gather stage alone,
-        // on what a preceding full call left in the workspace)
-        // Its workgroups WAIT for the medians, so the grid must not exceed what is resident at once for THIS instantiation
-        // (a late workgroup would start its two halves when the others end theirs): capacity per variant, cached in
-        // slots 4.. of the device cache.
-        unsigned fgrid = pgrid;
-        if (band) {
-            // BAND variants: medians always inside the launch (run_prep false only skips the segment launch: the keys of the
-            // preceding full call are still in the workspace), grid = resident capacity of the variant
-            fgrid = band_grid(tpw);
-#define DSS_LAUNCH_RB_B(CC, TT, YY)                                                                                         \
-    hipLaunchKernelGGL((render_backward_kernel<CC, true, TT, true, YY, true, true>), dim3(fgrid), dim3(256), 0, st, grad_out, alpha, idx, \
-                       qvalue, wsum, scaler, points, radii, rs, first_idx, num_pts, vis_count, vis_list, n_seg, seg_pts, N, S, K, C, \
-                       clip, row0, rows, large_waves, grad_feat, grad_pts, tshift, nullptr, nullptr, FP, astride, OW)
-            if (C == 3 && cyc) { if (tpw == 4) DSS_LAUNCH_RB_B(3, 4, true); else if (tpw == 2) DSS_LAUNCH_RB_B(3, 2, true); else DSS_LAUNCH_RB_B(3, 1, true); }
-            else if (C == 3) { if (tpw == 4) DSS_LAUNCH_RB_B(3, 4, false); else if (tpw == 2) DSS_LAUNCH_RB_B(3, 2, false); else DSS_LAUNCH_RB_B(3, 1, false); }
-            else { if (tpw == 4) DSS_LAUNCH_RB_B(0, 4, false); else if (tpw == 2) DSS_LAUNCH_RB_B(0, 2, false); else DSS_LAUNCH_RB_B(0, 1, false); }
-#undef DSS_LAUNCH_RB_B
-            return check_launch("dss_render_backward");
-        }
-        if (run_prep && fused_opt != 5) {
-            const int slot = 4 + (C == 3 ? 0 : 3) + (tpw == 4 ? 2 : (tpw == 2 ? 1 : 0));
-            int fcap = dc ? dc[slot].load(std::memory_order_relaxed) : 0;
-            if (fcap == 0) {
-                int per_cu = 0;
-#define DSS_OCC_F(CC, TT) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_backward_kernel<CC, true, TT, true, false, true>, 256, 0)
-                if (C == 3) { if (tpw == 4) DSS_OCC_F(3, 4); else if (tpw == 2) DSS_OCC_F(3, 2); else DSS_OCC_F(3, 1); }
-                else { if (tpw == 4) DSS_OCC_F(0, 4); else if (tpw == 2) DSS_OCC_F(0, 2); else DSS_OCC_F(0, 1); }
-#undef DSS_OCC_F
-                (void)hipGetLastError();
-                fcap = n_cus * (per_cu > 0 ? per_cu : 1);
-                if (dc) dc[slot].store(fcap, std::memory_order_relaxed);
-            }
-            if ((unsigned)fcap < fgrid) fgrid = (unsigned)fcap;
-            if (fgrid < (unsigned)N + 8u) fgrid = (unsigned)N + 8u;
-        }
-#define DSS_LAUNCH_RB_F(CC, TT, PP)                                                                                         \
-    hipLaunchKernelGGL((render_backward_kernel<CC, true, TT, true, false, PP>), dim3(fgrid), dim3(256), 0, st, grad_out, alpha, idx, \
-                       qvalue, wsum, scaler, points, radii, rs, first_idx, num_pts, vis_count, vis_list, n_seg, seg_pts, N, S, K, C, \
-                       clip, row0, rows, large_waves, grad_feat, grad_pts, 3, world, Mproj, FP, astride, OW)
-#define DSS_LAUNCH_RB_FT(CC, PP)                                                                                            \
-    do {                                                                                                                   \
-        if (tpw == 4) DSS_LAUNCH_RB_F(CC, 4, PP); else if (tpw == 2) DSS_LAUNCH_RB_F(CC, 2, PP); else DSS_LAUNCH_RB_F(CC, 1, PP); \
-    } while (0)
-        if (run_prep && fused_opt != 5) { if (C == 3) DSS_LAUNCH_RB_FT(3, true); else DSS_LAUNCH_RB_FT(0, true); }
-        else { if (C == 3) DSS_LAUNCH_RB_FT(3, false); else DSS_LAUNCH_RB_FT(0, false); }
-#undef DSS_LAUNCH_RB_FT
-#undef DSS_LAUNCH_RB_F
-        return check_launch("dss_render_backward");
+
+    // ---- the gather launch
+    const GatherKernel fn = gather_kernel(v);
+    if (!fn) {
+        // (only a tile-row-cyclic band gets here without a variant: built for the training configuration -- RGB features,
+        // 32-bit offsets)
+        set_error("dss_render_backward: a tile-row-cyclic band needs C == 3 and gathered tensors below 4 GB");
+        return DSS_ERR_UNSUPPORTED;
     }
-    // The grid is persistent and was sized for the variant the device cache measured (<C, true, 4, true>: 79 VGPRs, six
-    // workgroups per CU); some variants hold more registers (two tasks per wavefront without the fused preparation: 83, the
-    // 64-bit addressing: 100) -- a workgroup that is not resident at launch would start its share when the others end theirs,
-    // so every launch is clamped to what ITS instantiation keeps resident (occupancy queried once per instantiation).
-    auto resident_grid = [&](const void *fn) -> unsigned {
-        static std::atomic<const void *> keys[64];
-        static std::atomic<int> vals[64];
-        int per_cu = 0;
-        for (int i = 0; i < 64; ++i) {
-            const void *k = keys[i].load(std::memory_order_acquire);
-            if (k == fn) { per_cu = vals[i].load(std::memory_order_relaxed); break; }
-            if (k == nullptr) {
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
-                (void)hipGetLastError();
-                if (per_cu < 1) per_cu = 1;
-                const void *expect = nullptr;
-                if (keys[i].compare_exchange_strong(expect, fn, std::memory_order_acq_rel)) vals[i].store(per_cu, std::memory_order_relaxed);
-                break;   // (lost the race for the slot: this call uses its own query, a later one finds the entry or the next slot)
-            }
-        }
-        if (per_cu < 1) return pgrid;
-        const unsigned g = (unsigned)n_cus * (unsigned)per_cu;
-        return g < pgrid ? g : pgrid;
-    };
-#define DSS_LAUNCH_RB_A(CC, SS, TT, AA)                                                                                 \
-    hipLaunchKernelGGL((render_backward_kernel<CC, SS, TT, AA>), dim3(resident_grid((const void *)render_backward_kernel<CC, SS, TT, AA>)), dim3(256), 0, st, grad_out, alpha, idx, qvalue, wsum, \
-                       scaler, points, radii, rs, first_idx, num_pts, vis_count, vis_list, n_seg, seg_pts, N, S, K, C, clip, \
-                       row0, rows, large_waves, grad_feat, grad_pts, 3, world, Mproj, FusedPrep(), 1, OW)
-#define DSS_LAUNCH_RB(CC, SS, TT) DSS_LAUNCH_RB_A(CC, SS, TT, true)
-#define DSS_LAUNCH_RB_T(CC, SS)                                                                                        \
-    do {                                                                                                               \
-        if (!a32) DSS_LAUNCH_RB_A(CC, SS, 4, false);                                                                   \
-        else if (tpw == 4) DSS_LAUNCH_RB(CC, SS, 4); else if (tpw == 2) DSS_LAUNCH_RB(CC, SS, 2); else DSS_LAUNCH_RB(CC, SS, 1); \
-    } while (0)
-    if (cyc) {
-        // tile-row-cyclic band (multi-GPU): built for the training configuration (RGB features, 32-bit offsets)
-        if (C != 3 || !a32) {
-            set_error("dss_render_backward: a tile-row-cyclic band needs C == 3 and gathered tensors below 4 GB");
-            return DSS_ERR_UNSUPPORTED;
-        }
-#define DSS_LAUNCH_RB_C(SS, TT)                                                                                          \
-    hipLaunchKernelGGL((render_backward_kernel<3, SS, TT, true, true>), dim3(resident_grid((const void *)render_backward_kernel<3, SS, TT, true, true>)), dim3(256), 0, st, grad_out, alpha, idx, qvalue, \
-                       wsum, scaler, points, radii, rs, first_idx, num_pts, vis_count, vis_list, n_seg, seg_pts, N, S, K, C, clip, \
-                       row0, rows, large_waves, grad_feat, grad_pts, tshift, nullptr, nullptr, FusedPrep(), 1, OW)
-        if (small) { if (tpw == 4) DSS_LAUNCH_RB_C(true, 4); else if (tpw == 2) DSS_LAUNCH_RB_C(true, 2); else DSS_LAUNCH_RB_C(true, 1); }
-        else { if (tpw == 4) DSS_LAUNCH_RB_C(false, 4); else if (tpw == 2) DSS_LAUNCH_RB_C(false, 2); else DSS_LAUNCH_RB_C(false, 1); }
-#undef DSS_LAUNCH_RB_C
-    } else if (C == 3) {
-        if (small) DSS_LAUNCH_RB_T(3, true); else DSS_LAUNCH_RB_T(3, false);
-    } else {
-        if (small) DSS_LAUNCH_RB_T(0, true); else DSS_LAUNCH_RB_T(0, false);
-    }
-#undef DSS_LAUNCH_RB_T
-#undef DSS_LAUNCH_RB
-#undef DSS_LAUNCH_RB_A
+    hipLaunchKernelGGL(fn, dim3(gather_grid(v, fused)), dim3(256), 0, st, grad_out, alpha, idx, qvalue, wsum, scaler,
+                       points, radii, rs, first_idx, num_pts, vis_count, vis_list, n_seg, seg_pts, N, S, K, C, clip, row0, rows,
+                       large_waves, grad_feat, grad_pts, tshift, world, Mproj, FP, 1, OW);
     return check_launch("dss_render_backward");
 }
 

@@ -408,9 +408,15 @@ def blend_backward(grad_out, idx, qvalue, scaler, num_points: int, geometry=None
     return gf, grad_out[..., C]
 
 
-def backward_addr64() -> int:
-    """current value of DSS_OPT_BACKWARD_ADDR64 (1 forces the 64-bit gather, which has no fused projection)"""
-    return int(_lib.load().dss_get_option(_lib.OPT_BACKWARD_ADDR64))
+def fuse_projection(N: int, S: int, K: int, C: int, shared: bool, n_world: int, P: int) -> bool:
+    """whether `render_backward(..., project=(world, M))` can take the projection backward of a whole-image render of N
+    cameras, K fragments per pixel and C feature channels: only for RGB features, clouds that are not shared between
+    cameras (or one camera), one world point per screen point, and on the 32-bit-offset variants of the gather (every
+    gathered tensor below 4 GB and DSS_OPT_BACKWARD_ADDR64 off, raster_backward.hip).  Otherwise the separate projection
+    kernel runs (`project_backward`)."""
+    widest = N * S * S * max(K, C + 1) * 4
+    return (not shared or N == 1) and C == 3 and n_world == P and widest < (1 << 32) \
+        and int(_lib.load().dss_get_option(_lib.OPT_BACKWARD_ADDR64)) != 1
 
 
 def _band(rows, S):
@@ -626,39 +632,28 @@ def render_backward(grad_out, idx, qvalue, wsum, scaler, points, radii, visible,
                                    % (P, N, tuple(w_t.shape), tuple(m_t.shape)))
             w_p, m_p = _lib.ptr(w_t), _lib.ptr(m_t)
         ws = _lib.workspace(dev, lib.dss_render_backward_workspace(N, P, S))
+        # entry point by mode: the owner modes take the full-image gradient after grad_out and no projection
+        name, head, tail = "dss_render_backward", [_lib.ptr(grad_out)], [w_p, m_p]
         if grad_occ_full is not None:
             if project is not None or gather_only_rs is not None or grad_out_full is not None:
                 raise RuntimeError("grad_occ_full (owner mode of a band) excludes project=, gather_only_rs= and grad_out_full=")
             plane = _lib.require_gpu(grad_occ_full, "grad_occ_full", _f32)
             if tuple(plane.shape) != (N, S, S):
                 raise RuntimeError("grad_occ_full must be (N,S,S) = %s, got %s" % ((N, S, S), tuple(plane.shape)))
-            rc = lib.dss_render_backward_owned_plane(
-                _lib.ptr(grad_out), _lib.ptr(plane), _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(wsum), _lib.ptr(scaler),
-                _lib.ptr(points), _lib.ptr(radii), _lib.ptr(vis), _lib.ptr(first), _lib.ptr(num), N, P, S, K, C, row0, row1, cyc,
-                float(radii_s), float(clip), _lib.ptr(gf), _lib.ptr(gp), _lib.ptr(rs), _lib.ptr(ws), ws.numel(),
-                _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_render_backward_owned_plane")
-            return (gf, gp, rs) if return_rs else (gf, gp)
-        if grad_out_full is not None:
+            name, head, tail = "dss_render_backward_owned_plane", head + [_lib.ptr(plane)], []
+        elif grad_out_full is not None:
             if project is not None or gather_only_rs is not None:
                 raise RuntimeError("grad_out_full (owner mode of a band) excludes project= and gather_only_rs=")
             full = _lib.require_gpu(grad_out_full, "grad_out_full", _f32)
             if tuple(full.shape) != (N, S, S, C + 1) or not full.is_contiguous():
                 raise RuntimeError("grad_out_full must be contiguous (N,S,S,C+1)")
-            rc = lib.dss_render_backward_owned(
-                _lib.ptr(grad_out), _lib.ptr(full), _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(wsum), _lib.ptr(scaler),
-                _lib.ptr(points), _lib.ptr(radii), _lib.ptr(vis), _lib.ptr(first), _lib.ptr(num), N, P, S, K, C, row0, row1, cyc,
-                float(radii_s), float(clip), _lib.ptr(gf), _lib.ptr(gp), _lib.ptr(rs), _lib.ptr(ws), ws.numel(),
-                _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_render_backward_owned")
-            return (gf, gp, rs) if return_rs else (gf, gp)
-        entry = lib.dss_render_backward if gather_only_rs is None else lib.dss_render_backward_gather
-        rc = entry(_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(wsum),
-                   _lib.ptr(scaler), _lib.ptr(points), _lib.ptr(radii), _lib.ptr(vis),
-                   _lib.ptr(first), _lib.ptr(num), N, P, S, K, C, row0, row1, cyc, float(radii_s),
-                   float(clip), _lib.ptr(gf), _lib.ptr(gp), _lib.ptr(rs), w_p, m_p, _lib.ptr(ws), ws.numel(),
+            name, head, tail = "dss_render_backward_owned", head + [_lib.ptr(full)], []
+        entry = getattr(lib, name if gather_only_rs is None else "dss_render_backward_gather")
+        rc = entry(*head, _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(wsum), _lib.ptr(scaler), _lib.ptr(points),
+                   _lib.ptr(radii), _lib.ptr(vis), _lib.ptr(first), _lib.ptr(num), N, P, S, K, C, row0, row1, cyc,
+                   float(radii_s), float(clip), _lib.ptr(gf), _lib.ptr(gp), _lib.ptr(rs), *tail, _lib.ptr(ws), ws.numel(),
                    _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_render_backward")
+    _lib.check(rc, name)
     return (gf, gp, rs) if return_rs else (gf, gp)
 
 

@@ -821,9 +821,7 @@ class _GraphedRender:
 
     def _fuse(self, world):
         plan = self.plan
-        widest = plan.N * plan.S * plan.S * max(plan.K, plan.C + 1) * 4
-        return (not self.shared or plan.N == 1) and plan.C == 3 and world.shape[0] == plan.P and widest < (1 << 32) \
-            and ops.backward_addr64() != 1
+        return ops.fuse_projection(plan.N, plan.S, plan.K, plan.C, self.shared, world.shape[0], plan.P)
 
     @staticmethod
     def signature(inputs):
@@ -868,9 +866,7 @@ class _RenderFusedLean(autograd.Function):
         M, V, first, num, radii_s, clip, shared = ctx.aux
         if not g_image.is_contiguous():
             g_image = g_image.contiguous()
-        widest = plan.N * plan.S * plan.S * max(plan.K, plan.C + 1) * 4
-        fuse = (not shared or plan.N == 1) and plan.C == 3 and world.shape[0] == plan.P and widest < (1 << 32) \
-            and ops.backward_addr64() != 1
+        fuse = ops.fuse_projection(plan.N, plan.S, plan.K, plan.C, shared, world.shape[0], plan.P)
         g_feat, g_pts = plan.backward(arena, g_image, first, num, radii_s, clip, world if fuse else None, M if fuse else None)
         if not fuse:
             g_pts = ops.project_backward(world, M, V, first, num, g_pts, plan.view(arena, "valid").view(torch.bool), shared)
@@ -900,12 +896,9 @@ class _RenderFused(autograd.Function):
     @staticmethod
     def backward(ctx, g_image, *unused):
         world, M, V, first_idx, num_points, idx, qv, wsum, scaler, pts_screen, radii, visible, valid = ctx.saved_tensors
-        # the projection rides in the gather's epilogue only on the 32-bit-offset variants of the kernel (every gathered
-        # tensor below 4 GB and DSS_OPT_BACKWARD_ADDR64 off, raster_backward.hip): larger renders take the 64-bit gather
-        # and the separate projection kernel instead of failing inside autograd
-        widest = idx.numel() // idx.shape[-1] * max(idx.shape[-1], g_image.shape[-1]) * 4
-        fuse = (not ctx.shared or M.shape[0] == 1) and g_image.shape[-1] == 4 and world.shape[0] == pts_screen.shape[0] \
-            and widest < (1 << 32) and ops.backward_addr64() != 1
+        # (larger renders take the 64-bit gather and the separate projection kernel instead of failing inside autograd)
+        N, S, _, K = idx.shape
+        fuse = ops.fuse_projection(N, S, K, g_image.shape[-1] - 1, ctx.shared, world.shape[0], pts_screen.shape[0])
         g_feat, g_pts = ops.render_backward(g_image.contiguous(), idx, qv, wsum, scaler, pts_screen, radii, visible,
                                             first_idx, num_points, ctx.radii_s, ctx.clip,
                                             project=(world, M) if fuse else None)

@@ -76,11 +76,11 @@ DSS_API const char *dss_last_error(void);
  *                           tested against the current K-th distance: knn.hip, knn_subsort_kernel).  Results do not depend
  *                           on it.
  *   DSS_OPT_BACKWARD_FUSED  launch form of dss_render_backward for short lists (P <= 262,144, whole image): 0 (default) =
- *                             automatic; 1 = the round-3 sequence (compaction | median | gather kernels); 4 = two launches
- *                             (segments + alpha plane | medians + gather: the gather's workgroups do the blend half of their
- *                             tasks while the first N of them select the medians); 5 = three (segments + alpha plane |
- *                             medians | gather).  4 and 5 use the bucket-sorted median of raster_backward.hip.  Results do
- *                             not depend on it.
+ *                             automatic (4); 4 = two launches (segments + alpha plane | medians + gather: the gather's
+ *                             workgroups do the blend half of their tasks while the first N of them select the medians);
+ *                             5 = three (segments + alpha plane | medians | gather); any other value (1, 3, ...) = the
+ *                             round-3 sequence (compaction | median | gather kernels).  4 and 5 use the bucket-sorted median
+ *                             of raster_backward.hip.  Results do not depend on it.
  * Returns DSS_ERR_INVALID_ARGUMENT for an unknown option or value. */
 #define DSS_OPT_LEAN_WORKSPACE 0
 #define DSS_OPT_BACKWARD_TPW 1
