@@ -278,11 +278,19 @@ __global__ __launch_bounds__(256) void knn_fill_kernel(const float *__restrict__
         for (int cam = c0; cam < c1; ++cam) {
             const float *vm = view.V + 16 * cam;
             const bool drop = !knn_kept(x, y, z, vm[2], vm[6], vm[10], vm[14], view.znear[cam], view.zfar[cam]);
-            const unsigned long long m = __ballot(drop);
-            // (one atomic per wavefront, and none once the flag is seen up: 12,000 atomics on eight words took 100 us at 8 x 100k)
-            if (drop && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m) &&
-                __hip_atomic_load(&view.culls[cam], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-                atomicOr(&view.culls[cam], 1u);
+            unsigned long long m = __ballot(drop);
+            // (one atomic per wavefront and camera, and none once the flag is seen up: 12,000 atomics on eight words took 100 us
+            // at 8 x 100k.)  mode 2: a wavefront that straddles a cloud boundary holds lanes of different cameras -- one leader
+            // per distinct camera among the dropping lanes, or the later cloud's flag is lost when all its dropped points sit in
+            // such a wavefront.  mode 1: every lane has the same camera, one trip.
+            while (m != 0ull) {   // (wave-uniform)
+                const int leader = __builtin_ctzll(m);
+                const int lcam = __shfl(cam, leader);
+                if ((threadIdx.x & 63) == leader &&
+                    __hip_atomic_load(&view.culls[lcam], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+                    atomicOr(&view.culls[lcam], 1u);
+                m &= ~__ballot(drop && cam == lcam);
+            }
         }
     }
 }
@@ -639,7 +647,8 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float *__restrict_
         if (FULL) {
             for (int k = 0; k < Krt; ++k) { dists[slot * Krt + k] = 0.0f; idx[slot * Krt + k] = 0; }
         } else {
-            kth_sqdist[slot] = 0.0f;
+            // (one cloud, several cameras: the slot of THIS camera's row -- every row of the result is defined everywhere)
+            kth_sqdist[(VIEW && view.mode == 1 ? (size_t)blockIdx.y * (size_t)P : (size_t)0) + (size_t)slot] = 0.0f;
         }
         return;
     }
@@ -941,7 +950,8 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
             if (FULL) {
                 for (int k = 0; k < Krt; ++k) { dists[slot * Krt + k] = 0.0f; idx[slot * Krt + k] = 0; }
             } else {
-                kth_sqdist[slot] = 0.0f;
+                // (one cloud, several cameras: the slot of THIS camera's row -- every row of the result is defined everywhere)
+                kth_base[(walk ? (size_t)cam_y * (size_t)P : (size_t)0) + (size_t)slot] = 0.0f;
             }
         }
         continue;
@@ -1616,7 +1626,7 @@ extern "C" int dss_cloud_mean_clamp(const float *values, const int64_t *first_id
 
 // dss_cloud_mean_clamp under the reference's depth culling, for clouds whose culled points are masked instead of dropped
 // (see renderable_sum_kernel).  values (Pw,) per WORLD point; shared_cloud = 1: one cloud of num_pts[0] points seen by N
-// cameras; workspace: 16 N bytes.
+// cameras; workspace: 512 N bytes (RENDERABLE_BLOCKS partial (sum, count) pairs of doubles per camera).
 extern "C" int dss_renderable_mean_clamp(const float *values, const float *world, const float *V, const float *znear,
                                          const float *zfar, const int64_t *first_idx, const int64_t *num_pts, int N,
                                          int shared_cloud, float scale, float lo, float hi, float fallback, int min_points,

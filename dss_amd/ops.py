@@ -1028,13 +1028,14 @@ def knn_kth_sqdist_view(points, cloud_to_packed_first_idx, num_points_per_cloud,
     """`knn_kth_sqdist` in the reference's order under depth culling (``dss_knn_kth_sqdist_view``): every camera drops the
     points outside its [znear, zfar] BEFORE the neighbour search (rasterizer.py:599, 183-217, 310-326).  ``shared_cloud``:
     one cloud, N cameras -> (N, P) (row c: among the points camera c keeps; 0 for the ones it drops); else cloud n belongs to
-    camera n -> (P,)."""
+    camera n -> (P,).  Packed slots outside every cloud (before ``first_idx[0]``, between clouds, behind the last one) are 0,
+    in every row."""
     lib = _lib.load()
     points = _lib.require_gpu(points, "points", _f32)
     dev = points.device
     first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
     num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    V = _lib.require_gpu(V, "V", _f32)
+    V =_lib.require_gpu(V, "V", _f32)
     znear = _lib.require_gpu(znear, "znear", _f32)
     zfar = _lib.require_gpu(zfar, "zfar", _f32)
     N, P, n_cams = first.shape[0], points.shape[0], V.shape[0]

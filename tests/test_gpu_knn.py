@@ -6,21 +6,13 @@ from scipy.spatial import cKDTree
 
 import scenes
 from dss_amd import ops
+from knn_reference import kth as _ref_kth, radius_stat as _ref_radius_stat
 from dss_amd.cameras import FoVPerspectiveCameras, look_at_view_transform
 from dss_amd.cloud import PointClouds3D
 from dss_amd.rasterizer import PointsRasterizationSettings, SurfaceSplatting
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _ref_kth(points, K):
-    if points.shape[0] == 0:
-        return np.zeros(0, np.float32)
-    k = min(K, points.shape[0])
-    d, _ = cKDTree(points.astype(np.float64)).query(points.astype(np.float64), k=k)
-    d = d.reshape(points.shape[0], -1)
-    return (d[:, -1] ** 2).astype(np.float32)
 
 
 @pytest.mark.parametrize("K", [1, 7, 12, 16])
@@ -144,19 +136,6 @@ def test_knn_points_lists_match_kdtree(K):
             sep[:, 1:] &= gap
             sep[:, :-1] &= gap
         assert (gi[:, :k][sep] == wi[sep]).all()
-
-
-def _ref_radius_stat(points, K, r):
-    """frnn_grid_points(K, r) followed by `sq_dist[:, :, 1:].max(-1)` (rasterizer.py:317-324): neighbours beyond r come back
-    as -1; the statistic is the farthest of the K - 1 nearest non-self neighbours that lies within r, -1 if there is none"""
-    P = points.shape[0]
-    if P == 0:
-        return np.zeros(0, np.float32)
-    k = min(K, P)
-    d, _ = cKDTree(points.astype(np.float64)).query(points.astype(np.float64), k=k)
-    d2 = d.reshape(P, -1)[:, 1:] ** 2
-    d2 = np.where(d2 <= float(r) ** 2, d2, -1.0)
-    return (d2.max(1) if d2.shape[1] else np.full(P, -1.0)).astype(np.float32)
 
 
 @pytest.mark.parametrize("r", [0.2, 0.05])
