@@ -121,6 +121,8 @@ class FoVPerspectiveCameras:
         version counter; the cache keeps the tensors alive so an address cannot be recycled).  A training loop asks
         for the same matrices every iteration, and each rebuild is ~20 tiny GPU launches (0.3 ms of host time)."""
         state = tuple(getattr(self, k) for k in self._STATE)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in state):
+            return build()   # differentiable cameras: the matrix carries the autograd graph of ONE backward, never cached
         key = tuple(t._version for t in state) + (self.degrees,)
         cache = self.__dict__.setdefault("_matrix_cache", {})
         hit = cache.get(name)

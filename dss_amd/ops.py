@@ -931,6 +931,35 @@ def project_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_clou
     return gw
 
 
+def camera_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_cloud, grad_screen, valid,
+                    shared_cloud: bool = False, clip: float = -1.0):
+    """grad of (NDC x, NDC y, view z) w.r.t. the camera matrices (``dss_camera_backward``; the counterpart of
+    `project_backward`, same inputs) -> (grad_M (N,4,4), grad_V (N,4,4)), fully written, bitwise reproducible.  From
+    there plain torch autograd carries on to ``R``, ``T``, ``fov``, ... of the camera object."""
+    lib = _lib.load()
+    world = _lib.require_gpu(world, "world", _f32)
+    dev = world.device
+    M = _lib.require_gpu(M, "M", _f32)
+    V = _lib.require_gpu(V, "V", _f32)
+    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
+    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    grad_screen = _lib.require_gpu(grad_screen, "grad_screen", _f32)
+    vis = _lib.require_gpu(_as_u8(valid), "valid", _u8)
+    N, Pw = first.shape[0], world.shape[0]
+    P = N * Pw if shared_cloud else Pw
+    if tuple(M.shape) != (N, 4, 4) or tuple(V.shape) != (N, 4, 4) or tuple(grad_screen.shape) != (P, 3) or vis.numel() != P:
+        raise RuntimeError("camera_backward: need M, V (N,4,4), grad_screen (P,3), valid (P,) with N=%d P=%d" % (N, P))
+    with torch.cuda.device(dev):
+        gM = torch.empty((N, 4, 4), dtype=_f32, device=dev)
+        gV = torch.empty((N, 4, 4), dtype=_f32, device=dev)
+        ws = _lib.workspace(dev, lib.dss_camera_backward_workspace(N, P))
+        rc = lib.dss_camera_backward(_lib.ptr(world), _lib.ptr(M), _lib.ptr(V), _lib.ptr(first), _lib.ptr(num), N, Pw,
+                                     int(shared_cloud), _lib.ptr(grad_screen), _lib.ptr(vis), float(clip), _lib.ptr(gM),
+                                     _lib.ptr(gV), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(rc, "dss_camera_backward")
+    return gM, gV
+
+
 def knn_kth_sqdist(points, cloud_to_packed_first_idx, num_points_per_cloud, K: int = 7, radius=None):
     """K-th smallest squared distance of every point to its own cloud (self included) -> (P,).
     Exact grid search in HIP; replaces frnn.frnn_grid_points / pytorch3d.ops.knn_points for the
@@ -1113,6 +1142,30 @@ def phong_backward(grad_out, world, normals, rgb, cloud_to_packed_first_idx, num
                                     _lib.ptr(gn), _lib.ptr(gc), _lib.stream_ptr(dev))
     _lib.check(rc, "dss_phong_backward")
     return gw, gn, gc
+
+
+def phong_backward_camera(grad_out, world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, ambient,
+                          diffuse_color, specular_color, light_vec, point_lights: bool, cam_center, shininess: float = 64.0,
+                          shared_cloud: bool = False):
+    """-> grad_cam (N,3): the shading's gradient w.r.t. the camera centres (``dss_phong_backward_camera``; same inputs as
+    `phong_backward`), bitwise reproducible."""
+    lib = _lib.load()
+    world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L = _phong_common(
+        world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
+        specular_color, light_vec, cam_center)
+    grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
+    if tuple(grad_out.shape) != (P, 3):
+        raise RuntimeError("phong_backward_camera: grad_out must be (P,3)")
+    dev = world.device
+    with torch.cuda.device(dev):
+        gcam = torch.empty((N, 3), dtype=_f32, device=dev)
+        ws = _lib.workspace(dev, lib.dss_camera_backward_workspace(N, P))
+        rc = lib.dss_phong_backward_camera(_lib.ptr(grad_out), _lib.ptr(world), _lib.ptr(normals), _lib.ptr(rgb),
+                                           _lib.ptr(first), _lib.ptr(num), N, Pw, int(shared_cloud), _lib.ptr(amb),
+                                           _lib.ptr(kd), _lib.ptr(ks), _lib.ptr(lv), L, int(point_lights), _lib.ptr(cam),
+                                           float(shininess), _lib.ptr(gcam), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(rc, "dss_phong_backward_camera")
+    return gcam
 
 
 def _mask_u8(mask, name, P, dev):

@@ -198,7 +198,8 @@ def rasterize_elliptical_points(pcls_screen, ellipse_params, cutoff_threshold, r
 
 class _ProjectAndSetup(autograd.Function):
     """Fused filter_renderable + transform + _get_per_point_info (rasterizer.py:219-254, 614, 525-565).
-    Differentiable output: pts_screen (the EWA terms are detached in the reference, :562-565)."""
+    Differentiable output: pts_screen (the EWA terms are detached in the reference, :562-565), w.r.t. the world points
+    and -- when they require grad -- the camera matrices M and V (`ops.camera_backward`)."""
 
     @staticmethod
     def forward(ctx, world, normals, h, M, V, znear, zfar, first_idx, num_points, image_size, cutoff, sigma,
@@ -215,8 +216,15 @@ class _ProjectAndSetup(autograd.Function):
     @staticmethod
     def backward(ctx, g_screen, *unused):
         world, M, V, first_idx, num_points, valid = ctx.saved_tensors
-        gw = ops.project_backward(world, M, V, first_idx, num_points, g_screen.contiguous(), valid, ctx.shared)
-        return (gw,) + (None,) * 15
+        g_screen = g_screen.contiguous()
+        need_cam = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        gw = gM = gV = None
+        if ctx.needs_input_grad[0] or not need_cam:
+            gw = ops.project_backward(world, M, V, first_idx, num_points, g_screen, valid, ctx.shared)
+        if need_cam:
+            # (g_screen arrives clipped from the rasterizer's backward: no clip here, like the projection above)
+            gM, gV = ops.camera_backward(world, M, V, first_idx, num_points, g_screen, valid, ctx.shared)
+        return (gw, None, None, gM, gV) + (None,) * 11
 
 
 _CAMERA_FIELDS = ("R", "T", "znear", "zfar", "fov", "aspect_ratio")
@@ -227,6 +235,11 @@ def _camera_state(cameras):
     re-assigned to a fresh tensor changes identity, one modified in place changes version (a fresh tensor's version is 0
     again, so the version alone is no key; the tuple keeps the objects alive, so an id cannot be recycled either)."""
     return tuple((n, getattr(cameras, n, None), getattr(getattr(cameras, n, None), "_version", 0)) for n in _CAMERA_FIELDS)
+
+
+def _camera_needs_grad(tensors) -> bool:
+    """whether this call differentiates w.r.t. one of these camera tensors (grad mode on and one of them requires grad)"""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
 def _kw_state(v):
@@ -374,7 +387,9 @@ class SurfaceSplatting(torch.nn.Module):
 
         A training loop calls this every iteration with the same tensors in a fresh cloud object: everything that
         only depends on WHICH tensors / cameras / settings these are (not on their values) is memoised on their
-        identities (+ the cameras' version counters); a caller-supplied ``Vrk_h`` then makes the call free of launches."""
+        identities (+ the cameras' version counters); a caller-supplied ``Vrk_h`` then makes the call free of launches.
+        Cameras that are being differentiated (a field requires grad, grad mode on) are never memoised: their matrices
+        carry the autograd graph of ONE iteration."""
         raster_settings = kwargs.get("raster_settings", self.raster_settings)
         cameras = kwargs.get("cameras", self.cameras)
         if cameras is None:
@@ -383,11 +398,12 @@ class SurfaceSplatting(torch.nn.Module):
         h_given = kwargs.get("Vrk_h", None)
         memo_key = None
         pl, nl = point_clouds.points_list(), point_clouds.normals_list()
+        cam_state = tuple(getattr(cameras, k, None) for k in ("R", "T", "znear", "zfar", "fov", "aspect_ratio"))
         # (only when the packed geometry IS the caller's tensor -- one cloud, or one tensor extended to the cameras: a
         # concatenation of several tensors is a copy that has to be rebuilt from their current values)
         if h_given is not None and (raster_settings.Vrk_invariant or raster_settings.Vrk_isotropic) and len(pl) >= 1 \
-                and all(t is pl[0] for t in pl) and nl is not None and all(t is nl[0] for t in nl):
-            cam_state = tuple(getattr(cameras, k, None) for k in ("R", "T", "znear", "zfar", "fov", "aspect_ratio"))
+                and all(t is pl[0] for t in pl) and nl is not None and all(t is nl[0] for t in nl) \
+                and not _camera_needs_grad(cam_state):
             memo_key = (id(cameras), tuple(id(t) for t in cam_state), tuple(getattr(t, "_version", 0) for t in cam_state),
                         tuple(id(t) for t in pl), None if nl is None else tuple(id(t) for t in nl),
                         tuple(t.shape[0] for t in pl), id(h_given), h_given._version, id(raster_settings),
@@ -444,7 +460,7 @@ class SurfaceSplatting(torch.nn.Module):
         a = dict(N=N, shared=shared, world=world, normals=normals, h=h.to(dev, torch.float32), M=M, V=V,
                  znear=znear, zfar=zfar, first_idx=first_idx, num_points=num_points,
                  out_clouds=out_clouds, raster_settings=raster_settings, vr6=vr6, frame_n=frame_n)
-        if memo_key is not None and world is pl[0] and normals is nl[0]:
+        if memo_key is not None and world is pl[0] and normals is nl[0] and not (M.requires_grad or V.requires_grad):
             # (only when the packed tensors ARE the caller's tensors: a duck-typed cloud whose points_packed() is a copy --
             # pytorch3d's torch.cat -- would otherwise be served a stale copy after an in-place optimiser step)
             # (the memo keeps the keyed objects alive -- an id cannot be recycled while it is the current entry)
@@ -660,8 +676,11 @@ class SurfaceSplatting(torch.nn.Module):
     def render_fused(self, point_clouds, point_clouds_filter=None, **kwargs):
         """Rasterize AND blend in the fused kernels (``dss_render_forward`` / ``dss_render_backward``):
         -> ``(images (N,S,S,C+1), PointFragments, point_clouds)``.  Same values as ``forward`` + the
-        renderer's blend; the autograd graph is one node, so gradients flow to the world points and the
-        features only (a loss on ``fragments.zbuf`` needs the unfused path)."""
+        renderer's blend; the autograd graph is one node, so gradients flow to the world points, the features and
+        -- when a camera tensor requires grad -- the camera matrices, from where torch autograd carries on to ``R``,
+        ``T``, ``fov``, ... (a loss on ``fragments.zbuf`` needs the unfused path).  Differentiable cameras take the general
+        node (`_RenderFused`: separate projection backward + `ops.camera_backward`); ``graphed=True`` and
+        ``row_partition=...`` do not carry camera gradients and raise NotImplementedError rather than drop them."""
         original_clouds = point_clouds
         if kwargs.get("graphed", False) and point_clouds_filter is None and not kwargs.get("want_fragments", True):
             # graphed replay of the SAME call as last time (same tensor objects, cameras, settings, h: the steady state of
@@ -675,6 +694,7 @@ class SurfaceSplatting(torch.nn.Module):
                         and kwargs.get("raster_settings", self.raster_settings) is k[5] and k[3]._version == k[6] \
                         and pl[0].data_ptr() == G.ptrs[0][0] and fl[0].data_ptr() == G.ptrs[9][0] \
                         and all(getattr(k[4], n, None) is t and getattr(t, "_version", 0) == v for n, t, v in k[7]) \
+                        and not _camera_needs_grad(t for _n, t, _v in k[7]) \
                         and k[8] == tuple(getattr(k[5], n, None) for n in PointsRasterizationSettings.__slots__):
                     return _RenderFusedGraphed.apply(pl[0], fl[0], G), None, point_clouds
         if not point_clouds.isempty():
@@ -692,9 +712,14 @@ class SurfaceSplatting(torch.nn.Module):
             raise ValueError("render_fused blends at most 8 feature channels, got %d (use the unfused forward() + "
                              "renderer for wider features)" % feats.shape[1])
         part = kwargs.get("row_partition", None)
+        cam_grad = _camera_needs_grad((a["M"], a["V"]))
+        if cam_grad and (part is not None or kwargs.get("graphed", False)):
+            raise NotImplementedError(
+                "%s does not carry gradients to the cameras (a camera tensor requires grad): render without it, or detach "
+                "the cameras" % ("row_partition=..." if part is not None else "graphed=True"))
         if part is not None:
             return self._render_sharded(a, feats, st, part, point_clouds_filter, original_clouds, **kwargs)
-        lean = self._lean_plan(a, feats, st)
+        lean = None if cam_grad else self._lean_plan(a, feats, st)   # (the lean node keeps M and V out of the graph)
         # renderer-owned cached point order (large clouds; include/dss_hip.h DSS_WS_ORDER_*): refreshed every k-th call
         order_refresh = int(kwargs.get("order_refresh", getattr(self, "order_refresh", 0)) or 0)
         if lean is not None:
@@ -875,7 +900,7 @@ class _RenderFusedLean(autograd.Function):
 
 class _RenderFused(autograd.Function):
     """One autograd node for the whole hot path: forward = dss_render_forward ([setup+bin] -> [fine+blend]),
-    backward = dss_render_backward (+clip) -> dss_project_backward."""
+    backward = dss_render_backward (+clip) -> dss_project_backward, and dss_camera_backward when M / V require grad."""
 
     @staticmethod
     def forward(ctx, world, features, normals, h, M, V, znear, zfar, first_idx, num_points, image_size,
@@ -898,11 +923,18 @@ class _RenderFused(autograd.Function):
         world, M, V, first_idx, num_points, idx, qv, wsum, scaler, pts_screen, radii, visible, valid = ctx.saved_tensors
         # (larger renders take the 64-bit gather and the separate projection kernel instead of failing inside autograd)
         N, S, _, K = idx.shape
-        fuse = ops.fuse_projection(N, S, K, g_image.shape[-1] - 1, ctx.shared, world.shape[0], pts_screen.shape[0])
+        # differentiable cameras: their reduction needs the SCREEN-space gradient, so the projection stays a launch of its own
+        need_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        fuse = not need_cam and ops.fuse_projection(N, S, K, g_image.shape[-1] - 1, ctx.shared, world.shape[0],
+                                                    pts_screen.shape[0])
         g_feat, g_pts = ops.render_backward(g_image.contiguous(), idx, qv, wsum, scaler, pts_screen, radii, visible,
                                             first_idx, num_points, ctx.radii_s, ctx.clip,
                                             project=(world, M) if fuse else None)
         # clouds that are not shared between cameras: the projection backward ran in the gather's epilogue (g_pts is
         # already the world-space gradient); a shared cloud sums its cameras in the separate kernel
         g_world = g_pts if fuse else ops.project_backward(world, M, V, first_idx, num_points, g_pts, valid, ctx.shared)
-        return (g_world, g_feat) + (None,) * 20
+        g_M = g_V = None
+        if need_cam:
+            # (the gather has applied the clip to g_pts: neither projection call clips again)
+            g_M, g_V = ops.camera_backward(world, M, V, first_idx, num_points, g_pts, valid, ctx.shared)
+        return (g_world, g_feat, None, None, g_M, g_V) + (None,) * 16

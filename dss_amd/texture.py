@@ -95,9 +95,14 @@ class _Phong(autograd.Function):
     def backward(ctx, g):
         world, normals, rgb, first, num, amb, kd, ks, vec, cam = ctx.saved_tensors
         point_lights, shininess, shared = ctx.cfg
-        gw, gn, gc = ops.phong_backward(g.contiguous(), world, normals, rgb, first, num, amb, kd, ks, vec, point_lights,
+        g = g.contiguous()
+        gw, gn, gc = ops.phong_backward(g, world, normals, rgb, first, num, amb, kd, ks, vec, point_lights,
                                         cam, shininess, shared)
-        return (gw, gn, gc) + (None,) * 10
+        gcam = None
+        if ctx.needs_input_grad[9]:   # differentiable cameras: the view direction's way back to the camera centre
+            gcam = ops.phong_backward_camera(g, world, normals, rgb, first, num, amb, kd, ks, vec, point_lights, cam,
+                                             shininess, shared)
+        return (gw, gn, gc) + (None,) * 6 + (gcam,) + (None,) * 3
 
 
 class LightingTexture(torch.nn.Module):

@@ -452,6 +452,28 @@ DSS_API int dss_project_backward_features(const float *world, const float *M, co
                                           float *grad_world, const float *grad_feat /* (P,C) */, int C,
                                           float *grad_feat_world /* (Pw,C) */, void *stream);
 
+/* Backward of the same projection w.r.t. the CAMERAS.  In the reference the camera matrices are ordinary tensors of the
+ * autograd graph: SurfaceSplatting.forward projects with pytorch3d's transform (DSS/core/rasterizer.py:614),
+ * EllipticalRasterizer.backward hands pts_grad back to it (:975-977) and the clip hook (:667-673) sits on that tensor, so
+ * cameras.R / cameras.T with requires_grad receive pose gradients.  Row-vector convention, x = (x, y, z, 1),
+ * clip = x @ M[n], ndc = clip.xy / clip.w, view_z = (x @ V[n]).z; g = grad_screen of the pair after the clip (clip > 0: the
+ * arithmetic of dss_project_backward; clip <= 0: none), pairs with valid == 0 contribute nothing:
+ *   grad_M[n][:, 0] = sum_p x gx / w      grad_M[n][:, 1] = sum_p x gy / w      grad_M[n][:, 2] = 0
+ *   grad_M[n][:, 3] = sum_p x (-(gx ndc_x + gy ndc_y) / w)      grad_V[n][:, 2] = sum_p x gz, its other columns 0.
+ * Inputs as dss_project_backward.  grad_M, grad_V (N,4,4) are fully written on every call (Pw == 0 and cameras without a
+ * valid point: exact zeros).  Bitwise reproducible and independent of the device: no atomics; two launches -- one fp32
+ * partial per workgroup under an assignment of (camera, point range) to workgroups that depends on (N, Pw) only, then
+ * every camera's partials added in index order in fp64.  The workspace holds the partials
+ * (dss_camera_backward_workspace(N, P), P = number of packed pairs; also enough for dss_phong_backward_camera); a NULL
+ * or short workspace is reported as DSS_ERR_INVALID_ARGUMENT like every other argument of these two entries. */
+DSS_API size_t dss_camera_backward_workspace(int N, int64_t P);
+DSS_API int dss_camera_backward(const float *world, const float *M, const float *V,
+                                const int64_t *first_idx, const int64_t *num_pts, int N, int64_t Pw,
+                                int shared_cloud, const float *grad_screen /* (P,3) */,
+                                const uint8_t *valid /* (P,) */, float clip,
+                                float *grad_M /* (N,4,4) */, float *grad_V /* (N,4,4) */,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * kNN statistic behind the source-space variance scale h (rasterizer.py:310-326, 366-388):
  * kth_sqdist[p] = K-th smallest squared distance from point p to the points of its own cloud,
@@ -537,6 +559,19 @@ DSS_API int dss_phong_backward(const float *grad_out, const float *world, const 
                                const float *light_vec, int L, int point_lights, const float *cam_center,
                                float shininess, float *grad_world, float *grad_normals, float *grad_rgb,
                                void *stream);
+/* Backward of the shading w.r.t. the CAMERA CENTRE: LightingTexture passes cameras.get_camera_center() to the specular
+ * term (DSS/core/texture.py:65-125, DSS/core/lighting.py:80-172: v^ = normalize(camera - x)), so an RGB loss reaches
+ * cameras.R / cameras.T through it as well.  grad_cam[n] = + sum over the points p of camera n of gw(n, p), the gradient
+ * of camera - x that dss_phong_backward subtracts from the point's grad_world.  Same arguments as dss_phong_backward with
+ * grad_cam (N,3) (fully written; zeros when specular_color == 0) and a workspace of dss_camera_backward_workspace(N, P)
+ * bytes in place of the three per-point outputs; same two-launch reduction as dss_camera_backward. */
+DSS_API int dss_phong_backward_camera(const float *grad_out, const float *world, const float *normals,
+                                      const float *rgb, const int64_t *first_idx, const int64_t *num_pts, int N,
+                                      int64_t Pw, int shared_cloud, const float *ambient,
+                                      const float *diffuse_color, const float *specular_color,
+                                      const float *light_vec, int L, int point_lights, const float *cam_center,
+                                      float shininess, float *grad_cam /* (N,3) */, void *workspace,
+                                      size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Point-cloud regularisers of the training iteration (the "both regularisers" of SURVEY 8f rank 2): ProjectionLoss
