@@ -125,6 +125,18 @@ static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Regions of a workspace, carved front to back; every region starts on a 256-byte boundary.  base == nullptr: size query.
+struct Bump {
+    char *base;
+    size_t used;
+    template <typename T> T *take(size_t count)
+    {
+        T *r = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += align_up(count * sizeof(T), 256);
+        return r;
+    }
+};
+
 int check_launch(const char *what);
 int option(int which);                         // api.hip: value set by dss_set_option (0 = default)
 int cu_count(int dev);                          // api.hip: compute units of device `dev` (cached per device)

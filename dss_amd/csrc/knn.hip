@@ -1384,19 +1384,63 @@ static size_t knn_cells(int N, int64_t P) { return (size_t)(N > 0 ? N : 1) * knn
 static int knn_blocks(int64_t P) { return (int)((knn_stride(P) - 1 + KNN_SCAN_BLOCK - 1) / KNN_SCAN_BLOCK); }
 
 #define KNN_MAX_VIEW_CAMS 1024
-extern "C" size_t dss_knn_workspace(int N, int64_t P)
-{
-    const size_t n = N > 0 ? N : 1, p = P > 0 ? P : 1;
-    return align_up(n * 6 * 4 * KNN_BB_WGS, 256) + align_up(n * sizeof(KnnGrid), 256) + align_up((knn_cells(N, P) + 1) * 4, 256) * 3 +
-           align_up(n * (size_t)knn_blocks(P) * 4, 256) + align_up(p * 4, 256) + align_up(p * 16, 256) +
-           (KNN_MAX_VIEW_CAMS + 64) * 4 +   // dss_knn_kth_sqdist_view: one "drops points" flag per camera; the "dense cells" flag
-           align_up((p / KNN_BLOCK + 1) * 32, 256) +  // the block boxes of the skip structure (knn_subsort_kernel)
-           align_up((p / KNN_DENSE_CELL + 1) * 8, 256) +  // and its list of dense cells
-           align_up(p * 4, 256) * 3;                   // arrival numbers (knn_count_kernel); dss_knn_kth_sqdist_view: the unmasked search's two rows
-}
-
 #define KNN_FULL_MAX_K 40
 #define KNN_COOP_KTH_MAX_P 120000   // K-th distance: crossover of the two query kernels between 65k (cooperative +24 %) and 131k points (tie), profiles/r4_d_knn_sweep.json
+
+// The regions of the workspace.  A function of (N, P) alone, so that the size query and the call agree.
+struct KnnWorkspace {
+    int *bbox;                           // (N, 6) box per cloud as ordered ints, or the small form's partial boxes (N, KNN_BB_WGS, 6)
+    KnnGrid *grids;                      // (N)
+    uint32_t *counts, *offsets, *cursor; // (cells + 1) each, `cbytes` bytes: points per cell, its scan, the fill's write heads
+    uint32_t *blk_tot;                   // (N, nblk) block totals of the two-level scan
+    int32_t *cell_of;                    // (P) cell of every point (-1: not in a cloud, or NaN)
+    float4 *sorted;                      // (P) xyz + id, grouped by cell
+    uint32_t *cam_flags;                 // dss_knn_kth_sqdist_view: one "drops points" flag per camera (knn_fill_kernel)
+    uint32_t *dense_flag, *n_dense, *n_dense_pts;   // the "dense cells" flag and the two counters of the dense-cell list: KNN_DENSE_WORDS
+                                                    // words at the head of one 256-byte block, cleared together (knn_dense_list_kernel, knn_subsort_kernel)
+    float4 *boxes;                       // the block boxes of the skip structure (knn_subsort_kernel, knn_block_box_kernel)
+    uint2 *dense_list;                   // and its list of dense cells
+    uint32_t *rank_of;                   // (P) arrival numbers (knn_count_kernel)
+    float *plain_stat, *plain_dk;        // (P) each, dss_knn_kth_sqdist_view: the unmasked search's two rows
+    size_t stride;                       // per-cloud stride of the cell arrays
+    int nblk;                            // scan workgroups per cloud
+    size_t cbytes;                       // bytes of one cell array
+    size_t bytes;
+};
+#define KNN_DENSE_WORDS 3
+
+// ws == nullptr: size query (bytes)
+static KnnWorkspace carve_knn(void *ws, int N, int64_t P)
+{
+    KnnWorkspace w = {};
+    const size_t n = N > 0 ? N : 1, p = P > 0 ? P : 1;
+    w.stride = knn_stride(P);
+    w.nblk = knn_blocks(P);
+    Bump b = {reinterpret_cast<char *>(ws), 0};
+    w.bbox = b.take<int>(n * 6 * KNN_BB_WGS);
+    w.grids = b.take<KnnGrid>(n);
+    const size_t cells_at = b.used;
+    w.counts = b.take<uint32_t>(knn_cells(N, P) + 1);
+    w.cbytes = b.used - cells_at;
+    w.offsets = b.take<uint32_t>(knn_cells(N, P) + 1);
+    w.cursor = b.take<uint32_t>(knn_cells(N, P) + 1);
+    w.blk_tot = b.take<uint32_t>(n * (size_t)w.nblk);
+    w.cell_of = b.take<int32_t>(p);
+    w.sorted = b.take<float4>(p);
+    w.cam_flags = b.take<uint32_t>(KNN_MAX_VIEW_CAMS);
+    w.dense_flag = b.take<uint32_t>(64);
+    w.n_dense = ws ? w.dense_flag + 1 : nullptr;
+    w.n_dense_pts = ws ? w.dense_flag + 2 : nullptr;
+    w.boxes = b.take<float4>((p / KNN_BLOCK + 1) * 2);
+    w.dense_list = b.take<uint2>(p / KNN_DENSE_CELL + 1);
+    w.rank_of = b.take<uint32_t>(p);
+    w.plain_stat = b.take<float>(p);
+    w.plain_dk = b.take<float>(p);
+    w.bytes = b.used;
+    return w;
+}
+
+extern "C" size_t dss_knn_workspace(int N, int64_t P) { return carve_knn(nullptr, N, P).bytes; }
 
 // Per-cloud bounding boxes as ordered ints (decode with ord2f), for callers outside this file (regularizers.hip).
 int dss::launch_cloud_bbox(const float *points, const int64_t *first_idx, const int64_t *num_pts, int N, int64_t P,
@@ -1408,11 +1452,211 @@ int dss::launch_cloud_bbox(const float *points, const int64_t *first_idx, const 
     return check_launch("cloud bbox");
 }
 
-// grid build + query; exactly one of (kth_sqdist) / (dists, idx) is written
+// How a call is searched, decided once from (P, K, lists or K-th distance) and DSS_OPT_KNN_QUERY
+struct QueryPlan {
+    bool skip;      // the skip structure is built and read (see knn_subsort_kernel)
+    bool coop;      // the cooperative kernel; else one thread per query
+    int k;          // K of the template instance
+    unsigned one_block, one_grid;   // the one-thread kernel's workgroup size and workgroups
+    unsigned chunks;                // the cooperative kernel's workgroups (256 / KNN_LPQ queries each)
+};
+static QueryPlan plan_query(int64_t P, int K, bool full)
+{
+    const int opt = option(DSS_OPT_KNN_QUERY);   // 0: by size, 1: cooperative, 2: one thread per query, 3: by size, no skip structure
+    QueryPlan q;
+    q.skip = P >= KNN_SKIP_MIN_P && opt != 3;   // (3: the uniform-grid walk whatever the cloud, for A/B)
+    // full lists: the cooperative kernel wins while the launch is latency-bound (32k points, K = 12: 58 us against
+    // ~100); at 100k points of an evenly sampled cloud the merges of (distance, id) lists cost more than the shorter
+    // chains save (182 vs 155 us) -- but the one-thread kernel falls off a cliff as soon as cells fill up (30-60 points
+    // per cell, the training loop on its way to the clustered state: 1.0 ms), the cooperative one does not
+    // K-th distance only: cooperative up to KNN_COOP_KTH_MAX_P points (tools/knn_sweep.py, profiles/r4_d_knn_sweep.json)
+    q.coop = opt == 1 || ((opt == 0 || opt == 3) && P <= KNN_COOP_KTH_MAX_P);
+    // cooperative kernel: 16 lanes per query (K <= 16); the one-thread-per-query kernel keeps the deep lists
+    if (full) q.k = K <= 8 ? 8 : (K <= 12 ? 12 /* the regularisers' knn_k (trainer.py:134-137) */ : (K <= 16 ? 16 : KNN_FULL_MAX_K));
+    else q.k = K <= 8 ? 8 : KNN_MAX_K;
+    if (q.k > KNN_MAX_K) q.coop = false;
+    // small inputs: one wavefront per workgroup, so that the few hundred wavefronts spread over all 256 CUs
+    q.one_block = P <= 131072 ? 64u : 256u;
+    q.one_grid = (unsigned)((P + q.one_block - 1) / q.one_block);
+    q.chunks = (unsigned)((P + (256 / KNN_LPQ) - 1) / (256 / KNN_LPQ));
+    return q;
+}
+
+// Everything about a call that its launches share
+struct KnnCall {
+    const char *who;
+    const float *points;
+    const int64_t *first_idx, *num_pts;
+    int N;
+    int64_t P;
+    int K;
+    float *dists;      // full lists (dss_knn_points), else nullptr
+    int64_t *idx;
+    float r2;
+    hipStream_t st;
+    KnnWorkspace w;
+    QueryPlan plan;
+};
+
+// One instantiation of knn_query_kernel<K, FULL, VIEW> / knn_query_coop_kernel<K, FULL, VIEW, SKIP> as data (the one-thread
+// kernel has no SKIP parameter: it reads the skip structure whenever it is handed one)
+struct QueryVariant {
+    int k;
+    bool full, view, skip;
+};
+using OneThreadKernel = decltype(&knn_query_kernel<8, false>);
+using CoopKernel = decltype(&knn_query_coop_kernel<8, false>);
+
+// The instantiations that exist, and no others (nullptr for any other combination):
+//   K-th distance <8|16, false>, lists <8|12|16|40, true>, per camera <8, false, true>
+static OneThreadKernel one_thread_kernel(const QueryVariant &v)
+{
+    if (v.view) return (v.k == 8 && !v.full) ? knn_query_kernel<8, false, true> : nullptr;
+    if (v.full)
+        return v.k == 8 ? knn_query_kernel<8, true>
+                        : (v.k == 12 ? knn_query_kernel<12, true>
+                                     : (v.k == 16 ? knn_query_kernel<16, true>
+                                                  : (v.k == KNN_FULL_MAX_K ? knn_query_kernel<KNN_FULL_MAX_K, true> : nullptr)));
+    return v.k == 8 ? knn_query_kernel<8, false> : (v.k == KNN_MAX_K ? knn_query_kernel<KNN_MAX_K, false> : nullptr);
+}
+
+template <int K, bool FULL, bool VIEW>
+static CoopKernel coop_by_skip(bool skip)
+{
+    return skip ? knn_query_coop_kernel<K, FULL, VIEW, true> : knn_query_coop_kernel<K, FULL, VIEW, false>;
+}
+//   K-th distance <8|16, false>, lists <8|12|16, true>, per camera <8, false, true>, each with and without SKIP
+static CoopKernel coop_kernel(const QueryVariant &v)
+{
+    if (v.view) return (v.k == 8 && !v.full) ? coop_by_skip<8, false, true>(v.skip) : nullptr;
+    if (v.full)
+        return v.k == 8 ? coop_by_skip<8, true, false>(v.skip)
+                        : (v.k == 12 ? coop_by_skip<12, true, false>(v.skip) : (v.k == 16 ? coop_by_skip<16, true, false>(v.skip) : nullptr));
+    return v.k == 8 ? coop_by_skip<8, false, false>(v.skip) : (v.k == KNN_MAX_K ? coop_by_skip<KNN_MAX_K, false, false>(v.skip) : nullptr);
+}
+
+static int no_query_kernel(const KnnCall &c, const QueryVariant &v)
+{
+    set_error("%s: internal error, no query kernel <%d, %d, %d, %d>", c.who, v.k, (int)v.full, (int)v.view, (int)v.skip);
+    return DSS_ERR_UNSUPPORTED;
+}
+
+// The two query launch sites.  `out`: the K-th distance row(s) (nullptr with full lists).  role 0: the launch takes every
+// cloud (and uses the skip structure where `dense_flag` is up); 1: only clouds without dense cells; 2: only clouds with.
+// dk_out: the K-th distance itself (the unmasked search of the per-camera statistic); plain_stat / plain_dk: that search's
+// two rows, read by the per-camera launch (`view`).
+static int launch_one_thread(const KnnCall &c, const QueryVariant &v, dim3 grid, float *out, const KnnView &view, int role,
+                             float *dk_out, const float *plain_stat, const float *plain_dk)
+{
+    const OneThreadKernel fn = one_thread_kernel(v);
+    if (!fn) return no_query_kernel(c, v);
+    hipLaunchKernelGGL(fn, grid, dim3(c.plan.one_block), 0, c.st, c.points, c.first_idx, c.num_pts, c.N, c.P, c.w.grids, c.w.stride,
+                       c.w.offsets, c.w.sorted, c.K, out, c.dists, c.idx, c.r2, view, c.plan.skip ? c.w.boxes : nullptr,
+                       c.plan.skip ? c.w.dense_flag : nullptr, role, dk_out, plain_stat, plain_dk);
+    return DSS_OK;
+}
+// chunks: per-camera launch only, the query chunks per camera (its grid is persistent)
+static int launch_coop(const KnnCall &c, const QueryVariant &v, dim3 grid, float *out, const KnnView &view, unsigned chunks,
+                       int role, float *dk_out, const float *plain_stat, const float *plain_dk)
+{
+    const CoopKernel fn = coop_kernel(v);
+    if (!fn) return no_query_kernel(c, v);
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, c.st, c.points, c.first_idx, c.num_pts, c.N, c.P, c.w.grids, c.w.stride, c.w.offsets,
+                       c.w.sorted, c.K, out, c.dists, c.idx, c.r2, view, chunks, c.plan.skip ? c.w.boxes : nullptr,
+                       c.plan.skip ? c.w.dense_flag : nullptr, role, dk_out, plain_stat, plain_dk);
+    return DSS_OK;
+}
+
+// Cell grid of every cloud and the points grouped by cell (w.grids, w.offsets, w.sorted); with `view`, the cameras' flags
+static int build_grid(const KnnCall &c, const KnnView &view)
+{
+    const KnnWorkspace &w = c.w;
+    const unsigned pb = (unsigned)((c.P + 255) / 256);
+    if (c.P <= KNN_SMALL_P && c.N <= KNN_GRID_LDS && w.nblk <= KNN_SCAN1_BLOCKS) {
+        // small inputs: four launches instead of eight (see knn_bbox_partial_kernel)
+        int *partial = w.bbox;   // (N, KNN_BB_WGS, 6)
+        const unsigned zero_wgs = (unsigned)((w.stride + 4095) / 4096);
+        hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(KNN_BB_WGS + (zero_wgs ? zero_wgs : 1), c.N), dim3(256), 0, c.st, c.points,
+                           c.first_idx, c.num_pts, c.P, partial, w.counts, w.stride);
+        hipLaunchKernelGGL(knn_count_grid_kernel, dim3(pb), dim3(256), 0, c.st, c.points, c.first_idx, c.num_pts, c.N, c.P, partial,
+                           knn_res_cap(c.P), w.grids, w.stride, w.counts, w.cell_of);
+        hipLaunchKernelGGL(knn_scan_single_kernel, dim3(w.nblk, c.N), dim3(1024), 0, c.st, w.counts, w.grids, w.stride, w.offsets,
+                           w.cursor);
+        hipLaunchKernelGGL(knn_fill_kernel, dim3(pb), dim3(256), 0, c.st, c.points, c.first_idx, c.num_pts, c.N, c.P, w.cell_of,
+                           w.stride, w.cursor, w.sorted, view);
+        return DSS_OK;
+    }
+    if (hipMemsetAsync(w.counts, 0, w.cbytes, c.st) != hipSuccess) return check_launch("knn memset");
+    if (int rc = launch_cloud_bbox(c.points, c.first_idx, c.num_pts, c.N, c.P, w.bbox, c.st)) return rc;
+    hipLaunchKernelGGL(knn_grid_kernel, dim3((c.N + 63) / 64), dim3(64), 0, c.st, w.bbox, c.num_pts, c.N, knn_res_cap(c.P), w.grids);
+    hipLaunchKernelGGL(knn_count_kernel, dim3(pb), dim3(256), 0, c.st, c.points, c.first_idx, c.num_pts, c.N, c.P, w.grids, w.stride,
+                       w.counts, w.cell_of, w.rank_of);
+    hipLaunchKernelGGL(knn_scan_local_kernel, dim3(w.nblk, c.N), dim3(256), 0, c.st, w.counts, w.grids, w.stride, w.nblk, w.offsets,
+                       w.blk_tot);
+    hipLaunchKernelGGL(knn_scan_add_kernel, dim3(w.nblk, c.N), dim3(256), 0, c.st, w.grids, w.stride, w.nblk, w.blk_tot, w.offsets,
+                       w.cursor);
+    hipLaunchKernelGGL(knn_fill_kernel, dim3(pb), dim3(256), 0, c.st, c.points, c.first_idx, c.num_pts, c.N, c.P, w.cell_of, w.stride,
+                       w.offsets, w.sorted, view, w.rank_of);
+    return DSS_OK;
+}
+
+// The list of dense cells, their sub-sort and the block boxes (see knn_subsort_kernel)
+static void build_skip_structure(const KnnCall &c)
+{
+    const KnnWorkspace &w = c.w;
+    hipLaunchKernelGGL(knn_dense_list_kernel, dim3((unsigned)((w.stride + 254) / 256), c.N), dim3(256), 0, c.st, w.grids, w.stride,
+                       w.offsets, w.dense_list, w.n_dense, w.n_dense_pts);
+    hipLaunchKernelGGL(knn_subsort_kernel, dim3(KNN_SUBSORT_WGS), dim3(KNN_SUBSORT_THREADS), 0, c.st, w.grids, w.stride, w.offsets,
+                       c.first_idx, w.sorted, w.dense_list, w.n_dense, w.n_dense_pts, c.P, w.dense_flag);
+    hipLaunchKernelGGL(knn_block_box_kernel, dim3((unsigned)((c.P / KNN_BLOCK + 256) / 256)), dim3(256), 0, c.st, w.sorted, c.P,
+                       w.dense_flag, w.boxes);
+}
+
+// Every point among all the points of its cloud: `out` = the K-th distance row, or the lists of the call
+static int query_plain(const KnnCall &c, float *out, float *dk_out)
+{
+    const QueryPlan &q = c.plan;
+    const QueryVariant v = {q.k, c.dists != nullptr, false, q.skip};
+    if (q.coop) return launch_coop(c, v, dim3(q.chunks), out, KnnView(), 0u, 0, dk_out, nullptr, nullptr);
+    if (!q.skip || q.k > KNN_MAX_K) return launch_one_thread(c, v, dim3(q.one_grid), out, KnnView(), 0, dk_out, nullptr, nullptr);
+    // a size at which the one-thread kernel is the choice for an evenly sampled cloud, K <= 16: clouds with dense cells go to
+    // the cooperative kernel all the same (sixteen boxes tested per trip), as a second launch; each launch leaves at once
+    // when the cloud is not its kind
+    if (int rc = launch_one_thread(c, v, dim3(q.one_grid), out, KnnView(), 1, dk_out, nullptr, nullptr)) return rc;
+    return launch_coop(c, v, dim3(q.chunks), out, KnnView(), 0u, 2, dk_out, nullptr, nullptr);
+}
+
+// K-th distance under per-camera culling (K <= 8: the variance-scale statistic): one grid row per camera
+static int query_per_camera(const KnnCall &c, const KnnView &view, float *kth_sqdist)
+{
+    const QueryPlan &q = c.plan;
+    const KnnWorkspace &w = c.w;
+    // (1) the unmasked search of every point: statistic + K-th distance (see knn_view_shortcut)
+    if (int rc = query_plain(c, w.plain_stat, w.plain_dk)) return rc;
+    // (2) per camera: copy, or search again among the points the camera keeps
+    const QueryVariant masked = {q.k, false, true, q.skip};
+    if (q.coop) {
+        // one cloud, several cameras: the grid covers one camera's chunks (see knn_query_coop_kernel)
+        const dim3 grid = view.mode == 1 ? dim3(q.chunks < 16384u ? q.chunks : 16384u, view.n_cams > 1 ? 2u : 1u) : dim3(q.chunks);
+        if (int rc = launch_coop(c, masked, grid, kth_sqdist, view, q.chunks, 0, nullptr, w.plain_stat, w.plain_dk)) return rc;
+    } else {
+        const dim3 grid(q.one_grid, view.mode == 1 ? (unsigned)view.n_cams : 1u);
+        if (int rc = launch_one_thread(c, masked, grid, kth_sqdist, view, 0, nullptr, w.plain_stat, w.plain_dk)) return rc;
+    }
+    if (view.mode == 1)   // the rows of the cameras that drop nothing = the unmasked search
+        hipLaunchKernelGGL(knn_view_rows_kernel, dim3((unsigned)((c.P + 1023) / 1024), (unsigned)view.n_cams), dim3(256), 0, c.st,
+                           kth_sqdist, w.plain_stat, c.P, view.culls);
+    return DSS_OK;
+}
+
+// grid build + query; exactly one of (kth_sqdist) / (dists, idx) is written.  radius > 0: the fixed-radius semantics of
+// dss_knn_kth_sqdist_radius.  view.mode != 0: the per-camera search of view.n_cams cameras (view.culls is set here).
+// Stages: validate -> carve the workspace, choose the plan -> clear the flags -> grid -> skip structure -> query.
 static int knn_run(const char *who, const float *points, const int64_t *first_idx, const int64_t *num_pts, int N, int64_t P,
                    int K, float *kth_sqdist, float *dists, int64_t *idx, void *workspace, size_t workspace_bytes,
-                   void *stream, float r2 = -1.0f, KnnView view = KnnView(), int n_cams = 1)
+                   void *stream, float radius, KnnView view = KnnView())
 {
+    // ---- validate
     const bool full = dists != nullptr;
     if (N <= 0 || P < 0 || K < 1 || K > (full ? KNN_FULL_MAX_K : KNN_MAX_K)) {
         set_error("%s: bad sizes N=%d P=%lld K=%d (K <= %d)", who, N, (long long)P, K, full ? KNN_FULL_MAX_K : KNN_MAX_K);
@@ -1427,167 +1671,24 @@ static int knn_run(const char *who, const float *points, const int64_t *first_id
         set_error("%s: workspace too small", who);
         return DSS_ERR_WORKSPACE;
     }
-    hipStream_t st = as_stream(stream);
-    char *w = reinterpret_cast<char *>(workspace);
-    size_t off = 0;
-    int *bbox = reinterpret_cast<int *>(w + off);                 off += align_up((size_t)N * 6 * 4 * KNN_BB_WGS, 256);  // box, or the partial boxes
-    KnnGrid *grids = reinterpret_cast<KnnGrid *>(w + off);        off += align_up((size_t)N * sizeof(KnnGrid), 256);
-    const size_t cbytes = align_up((knn_cells(N, P) + 1) * 4, 256);
-    const size_t stride = knn_stride(P);
-    const int nblk = knn_blocks(P);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(w + off);     off += cbytes;
-    uint32_t *offsets = reinterpret_cast<uint32_t *>(w + off);    off += cbytes;
-    uint32_t *cursor = reinterpret_cast<uint32_t *>(w + off);     off += cbytes;
-    uint32_t *blk_tot = reinterpret_cast<uint32_t *>(w + off);    off += align_up((size_t)N * nblk * 4, 256);
-    int32_t *cell_of = reinterpret_cast<int32_t *>(w + off);      off += align_up((size_t)P * 4, 256);
-    float4 *sorted = reinterpret_cast<float4 *>(w + off);                    off += align_up((size_t)P * 16, 256);
-    uint32_t *flags = reinterpret_cast<uint32_t *>(w + off);         off += (KNN_MAX_VIEW_CAMS + 64) * 4;   // [cameras | dense]
-    float4 *boxes = reinterpret_cast<float4 *>(w + off);            off += align_up(((size_t)P / KNN_BLOCK + 1) * 32, 256);
-    uint2 *dense_list = reinterpret_cast<uint2 *>(w + off);         off += align_up(((size_t)P / KNN_DENSE_CELL + 1) * 8, 256);
-    uint32_t *rank_of = reinterpret_cast<uint32_t *>(w + off);      off += align_up((size_t)P * 4, 256);
-    float *plain_stat = reinterpret_cast<float *>(w + off);         off += align_up((size_t)P * 4, 256);
-    float *plain_dk = reinterpret_cast<float *>(w + off);           off += align_up((size_t)P * 4, 256);
-    uint32_t *dense_flag = flags + KNN_MAX_VIEW_CAMS, *n_dense = dense_flag + 1, *n_dense_pts = dense_flag + 2;
-    const bool skip = P >= KNN_SKIP_MIN_P && option(DSS_OPT_KNN_QUERY) != 3;   // (3: the uniform-grid walk whatever the cloud, for A/B)
     if (view.mode != 0) {
-        if (n_cams > KNN_MAX_VIEW_CAMS) { set_error("%s: at most %d cameras", who, KNN_MAX_VIEW_CAMS); return DSS_ERR_UNSUPPORTED; }
-        view.culls = flags;
-        view.n_cams = n_cams;
-        if (hipMemsetAsync(view.culls, 0, (size_t)n_cams * 4, st) != hipSuccess) return check_launch("knn view memset");
-    }
-    if (skip && hipMemsetAsync(dense_flag, 0, 12, st) != hipSuccess) return check_launch("knn flag memset");
-    const unsigned pb_s = (unsigned)((P + 255) / 256);
-    if (P <= KNN_SMALL_P && N <= KNN_GRID_LDS && nblk <= KNN_SCAN1_BLOCKS) {
-        // small inputs: four launches instead of eight (see knn_bbox_partial_kernel)
-        int *partial = bbox;   // (N, KNN_BB_WGS, 6)
-        const unsigned zero_wgs = (unsigned)((stride + 4095) / 4096);
-        hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(KNN_BB_WGS + (zero_wgs ? zero_wgs : 1), N), dim3(256), 0, st, points,
-                           first_idx, num_pts, P, partial, counts, stride);
-        hipLaunchKernelGGL(knn_count_grid_kernel, dim3(pb_s), dim3(256), 0, st, points, first_idx, num_pts, N, P, partial,
-                           knn_res_cap(P), grids, stride, counts, cell_of);
-        hipLaunchKernelGGL(knn_scan_single_kernel, dim3(nblk, N), dim3(1024), 0, st, counts, grids, stride, offsets, cursor);
-        hipLaunchKernelGGL(knn_fill_kernel, dim3(pb_s), dim3(256), 0, st, points, first_idx, num_pts, N, P, cell_of, stride,
-                           cursor, sorted, view);
-    } else {
-        if (hipMemsetAsync(counts, 0, cbytes, st) != hipSuccess) return check_launch("knn memset");
-        const unsigned pb = (unsigned)((P + 255) / 256);
-        if (int rc = launch_cloud_bbox(points, first_idx, num_pts, N, P, bbox, st)) return rc;
-        hipLaunchKernelGGL(knn_grid_kernel, dim3((N + 63) / 64), dim3(64), 0, st, bbox, num_pts, N, knn_res_cap(P), grids);
-        hipLaunchKernelGGL(knn_count_kernel, dim3(pb), dim3(256), 0, st, points, first_idx, num_pts, N, P, grids, stride,
-                           counts, cell_of, rank_of);
-        hipLaunchKernelGGL(knn_scan_local_kernel, dim3(nblk, N), dim3(256), 0, st, counts, grids, stride, nblk, offsets,
-                           blk_tot);
-        hipLaunchKernelGGL(knn_scan_add_kernel, dim3(nblk, N), dim3(256), 0, st, grids, stride, nblk, blk_tot, offsets, cursor);
-        hipLaunchKernelGGL(knn_fill_kernel, dim3(pb), dim3(256), 0, st, points, first_idx, num_pts, N, P, cell_of, stride,
-                           offsets, sorted, view, rank_of);
-    }
-    if (skip) {
-        hipLaunchKernelGGL(knn_dense_list_kernel, dim3((unsigned)((stride + 254) / 256), N), dim3(256), 0, st, grids, stride, offsets,
-                           dense_list, n_dense, n_dense_pts);
-        hipLaunchKernelGGL(knn_subsort_kernel, dim3(KNN_SUBSORT_WGS), dim3(KNN_SUBSORT_THREADS), 0, st, grids, stride, offsets, first_idx, sorted,
-                           dense_list, n_dense, n_dense_pts, P, dense_flag);
-        hipLaunchKernelGGL(knn_block_box_kernel, dim3((unsigned)((P / KNN_BLOCK + 256) / 256)), dim3(256), 0, st, sorted, P,
-                           dense_flag, boxes);
-    }
-    const float4 *bx = skip ? boxes : nullptr;
-    const uint32_t *df = skip ? dense_flag : nullptr;
-    // small inputs: one wavefront per workgroup, so that the few hundred wavefronts spread over all 256 CUs
-    const unsigned qt = P <= 131072 ? 64u : 256u;
-    const unsigned qb = (unsigned)((P + qt - 1) / qt);
-    const unsigned gy = view.mode == 1 ? (unsigned)n_cams : 1u;
-    // ROLE 0: the launch takes every cloud (and uses the skip structure where `dense_flag` is up); 2: it runs only for clouds
-    // with dense cells, next to a cooperative launch that leaves those alone
-#define KNN_LAUNCH_R(KK, FF, ROLE)                                                                                  \
-    hipLaunchKernelGGL((knn_query_kernel<KK, FF>), dim3(qb), dim3(qt), 0, st, points, first_idx, num_pts, N, P, grids,  \
-                       stride, offsets, sorted, K, kth_sqdist, dists, idx, r2, KnnView(), bx, df, ROLE)
-#define KNN_LAUNCH(KK, FF) KNN_LAUNCH_R(KK, FF, 0)
-    // cooperative kernel: 16 lanes per query (K <= 16); the one-thread-per-query kernel keeps the deep lists
-    const unsigned cb = (unsigned)((P + (256 / KNN_LPQ) - 1) / (256 / KNN_LPQ));
-#define KNN_LAUNCH_COOP_R(KK, FF, ROLE)                                                                             \
-    do {                                                                                                            \
-        if (skip)                                                                                                   \
-            hipLaunchKernelGGL((knn_query_coop_kernel<KK, FF, false, true>), dim3(cb), dim3(256), 0, st, points, first_idx, num_pts, \
-                               N, P, grids, stride, offsets, sorted, K, kth_sqdist, dists, idx, r2, KnnView(), 0u, bx, df, ROLE); \
-        else                                                                                                        \
-            hipLaunchKernelGGL((knn_query_coop_kernel<KK, FF>), dim3(cb), dim3(256), 0, st, points, first_idx, num_pts, N, P, \
-                               grids, stride, offsets, sorted, K, kth_sqdist, dists, idx, r2, KnnView(), 0u, bx, df, ROLE); \
-    } while (0)
-#define KNN_LAUNCH_COOP(KK, FF) KNN_LAUNCH_COOP_R(KK, FF, 0)
-    // a size at which the one-thread kernel is the choice for an evenly sampled cloud, K <= 16: clouds with dense cells go to
-    // the cooperative kernel all the same (sixteen boxes tested per trip), as a second launch; each launch leaves at once
-    // when the cloud is not its kind
-#define KNN_LAUNCH_BOTH(KK, FF)                                                                                     \
-    do {                                                                                                            \
-        if (skip) { KNN_LAUNCH_R(KK, FF, 1); KNN_LAUNCH_COOP_R(KK, FF, 2); } else KNN_LAUNCH(KK, FF);                 \
-    } while (0)
-    const int qopt = option(DSS_OPT_KNN_QUERY) == 3 ? 0 : option(DSS_OPT_KNN_QUERY);   // 0: by size, 1: cooperative, 2: one thread per query (3: by size, no skip structure)
-    if (view.mode != 0) {
-        // K-th distance under per-camera culling (K <= 8: the variance-scale statistic): one grid row per camera
+        if (view.n_cams > KNN_MAX_VIEW_CAMS) { set_error("%s: at most %d cameras", who, KNN_MAX_VIEW_CAMS); return DSS_ERR_UNSUPPORTED; }
         if (full || K > 8) { set_error("%s: the per-camera search is built for the K-th distance with K <= 8", who); return DSS_ERR_UNSUPPORTED; }
-        const bool coop = qopt == 1 || (qopt == 0 && P <= KNN_COOP_KTH_MAX_P);
-        // (1) the unmasked search of every point: statistic + K-th distance (see knn_view_shortcut)
-        if (coop) {
-            if (skip)
-                hipLaunchKernelGGL((knn_query_coop_kernel<8, false, false, true>), dim3(cb), dim3(256), 0, st, points, first_idx,
-                                   num_pts, N, P, grids, stride, offsets, sorted, K, plain_stat, dists, idx, r2, KnnView(), 0u, bx, df, 0,
-                                   plain_dk);
-            else
-                hipLaunchKernelGGL((knn_query_coop_kernel<8, false>), dim3(cb), dim3(256), 0, st, points, first_idx, num_pts, N, P,
-                                   grids, stride, offsets, sorted, K, plain_stat, dists, idx, r2, KnnView(), 0u, bx, df, 0, plain_dk);
-        } else if (skip) {
-            // (clouds with dense cells go to the cooperative kernel at every size, see KNN_LAUNCH_BOTH)
-            hipLaunchKernelGGL((knn_query_kernel<8, false>), dim3(qb), dim3(qt), 0, st, points, first_idx, num_pts, N, P, grids,
-                               stride, offsets, sorted, K, plain_stat, dists, idx, r2, KnnView(), bx, df, 1, plain_dk);
-            hipLaunchKernelGGL((knn_query_coop_kernel<8, false, false, true>), dim3(cb), dim3(256), 0, st, points, first_idx,
-                               num_pts, N, P, grids, stride, offsets, sorted, K, plain_stat, dists, idx, r2, KnnView(), 0u, bx, df, 2,
-                               plain_dk);
-        } else {
-            hipLaunchKernelGGL((knn_query_kernel<8, false>), dim3(qb), dim3(qt), 0, st, points, first_idx, num_pts, N, P, grids,
-                               stride, offsets, sorted, K, plain_stat, dists, idx, r2, KnnView(), bx, df, 0, plain_dk);
-        }
-        // (2) per camera: copy, or search again among the points the camera keeps
-        if (coop) {
-            // one cloud, several cameras: the grid covers one camera's chunks (see knn_query_coop_kernel)
-            const dim3 grid = view.mode == 1 ? dim3(cb < 16384u ? cb : 16384u, n_cams > 1 ? 2u : 1u) : dim3(cb);
-            if (skip)
-                hipLaunchKernelGGL((knn_query_coop_kernel<8, false, true, true>), grid, dim3(256), 0, st, points, first_idx,
-                                   num_pts, N, P, grids, stride, offsets, sorted, K, kth_sqdist, dists, idx, r2, view, cb, bx, df, 0,
-                                   nullptr, plain_stat, plain_dk);
-            else
-                hipLaunchKernelGGL((knn_query_coop_kernel<8, false, true>), grid, dim3(256), 0, st, points, first_idx, num_pts,
-                                   N, P, grids, stride, offsets, sorted, K, kth_sqdist, dists, idx, r2, view, cb, bx, df, 0, nullptr,
-                                   plain_stat, plain_dk);
-        } else {
-            hipLaunchKernelGGL((knn_query_kernel<8, false, true>), dim3(qb, gy), dim3(qt), 0, st, points, first_idx, num_pts, N, P,
-                               grids, stride, offsets, sorted, K, kth_sqdist, dists, idx, r2, view, bx, df, 0, nullptr, plain_stat,
-                               plain_dk);
-        }
-        if (view.mode == 1)   // the rows of the cameras that drop nothing = the unmasked search
-            hipLaunchKernelGGL(knn_view_rows_kernel, dim3((unsigned)((P + 1023) / 1024), (unsigned)n_cams), dim3(256), 0, st, kth_sqdist,
-                               plain_stat, P, view.culls);
-        return check_launch(who);
     }
-    if (full) {
-        // full lists: the cooperative kernel wins while the launch is latency-bound (32k points, K = 12: 58 us against
-        // ~100); at 100k points of an evenly sampled cloud the merges of (distance, id) lists cost more than the shorter
-        // chains save (182 vs 155 us) -- but the one-thread kernel falls off a cliff as soon as cells fill up (30-60 points
-        // per cell, the training loop on its way to the clustered state: 1.0 ms), the cooperative one does not
-        const bool coop = qopt == 1 || (qopt == 0 && P <= KNN_COOP_KTH_MAX_P);
-        if (K <= 8) { if (coop) KNN_LAUNCH_COOP(8, true); else KNN_LAUNCH_BOTH(8, true); }
-        else if (K <= 12) { if (coop) KNN_LAUNCH_COOP(12, true); else KNN_LAUNCH_BOTH(12, true); }  // the regularisers' knn_k (trainer.py:134-137)
-        else if (K <= 16) { if (coop) KNN_LAUNCH_COOP(16, true); else KNN_LAUNCH_BOTH(16, true); }
-        else KNN_LAUNCH(KNN_FULL_MAX_K, true);
-    } else {
-        // K-th distance only: cooperative up to KNN_COOP_KTH_MAX_P points (tools/knn_sweep.py, profiles/r4_d_knn_sweep.json)
-        const bool coop = qopt == 1 || (qopt == 0 && P <= KNN_COOP_KTH_MAX_P);
-        if (K <= 8) { if (coop) KNN_LAUNCH_COOP(8, false); else KNN_LAUNCH_BOTH(8, false); }
-        else { if (coop) KNN_LAUNCH_COOP(KNN_MAX_K, false); else KNN_LAUNCH_BOTH(KNN_MAX_K, false); }
+    // ---- carve, plan
+    const KnnCall c = {who, points, first_idx, num_pts, N, P, K, dists, idx, radius > 0.0f ? radius * radius : -1.0f,
+                       as_stream(stream), carve_knn(workspace, N, P), plan_query(P, K, full)};
+    // ---- clear the flags
+    if (view.mode != 0) {
+        view.culls = c.w.cam_flags;
+        if (hipMemsetAsync(view.culls, 0, (size_t)view.n_cams * 4, c.st) != hipSuccess) return check_launch("knn view memset");
     }
-#undef KNN_LAUNCH_BOTH
-#undef KNN_LAUNCH_COOP
-#undef KNN_LAUNCH_COOP_R
-#undef KNN_LAUNCH
-#undef KNN_LAUNCH_R
+    if (c.plan.skip && hipMemsetAsync(c.w.dense_flag, 0, KNN_DENSE_WORDS * 4, c.st) != hipSuccess) return check_launch("knn flag memset");
+    // ---- build
+    if (int rc = build_grid(c, view)) return rc;
+    if (c.plan.skip) build_skip_structure(c);
+    // ---- query
+    if (int rc = view.mode != 0 ? query_per_camera(c, view, kth_sqdist) : query_plain(c, kth_sqdist, nullptr)) return rc;
     return check_launch(who);
 }
 
@@ -1596,7 +1697,7 @@ extern "C" int dss_knn_kth_sqdist(const float *points, const int64_t *first_idx,
                                   void *stream)
 {
     return knn_run("dss_knn_kth_sqdist", points, first_idx, num_pts, N, P, K, kth_sqdist, nullptr, nullptr, workspace,
-                   workspace_bytes, stream);
+                   workspace_bytes, stream, 0.0f);
 }
 
 extern "C" int dss_knn_points(const float *points, const int64_t *first_idx, const int64_t *num_pts, int N, int64_t P,
@@ -1608,7 +1709,7 @@ extern "C" int dss_knn_points(const float *points, const int64_t *first_idx, con
         return DSS_ERR_INVALID_ARGUMENT;
     }
     return knn_run("dss_knn_points", points, first_idx, num_pts, N, P, K, nullptr, dists, idx, workspace, workspace_bytes,
-                   stream);
+                   stream, 0.0f);
 }
 
 extern "C" int dss_cloud_mean_clamp(const float *values, const int64_t *first_idx, const int64_t *num_pts, int N,
@@ -1656,7 +1757,7 @@ extern "C" int dss_knn_kth_sqdist_radius(const float *points, const int64_t *fir
                                          size_t workspace_bytes, void *stream)
 {
     return knn_run("dss_knn_kth_sqdist_radius", points, first_idx, num_pts, N, P, K, kth_sqdist, nullptr, nullptr, workspace,
-                   workspace_bytes, stream, radius > 0.0f ? radius * radius : -1.0f);
+                   workspace_bytes, stream, radius);
 }
 
 // dss_knn_kth_sqdist[_radius] in the reference's ORDER under depth culling: filter_renderable extends the cloud to the
@@ -1676,5 +1777,5 @@ extern "C" int dss_knn_kth_sqdist_view(const float *points, const int64_t *first
     }
     KnnView view = {V, znear, zfar, shared_cloud ? 1 : 2, nullptr, n_cams};
     return knn_run("dss_knn_kth_sqdist_view", points, first_idx, num_pts, N, P, K, kth_sqdist, nullptr, nullptr, workspace,
-                   workspace_bytes, stream, radius > 0.0f ? radius * radius : -1.0f, view, n_cams);
+                   workspace_bytes, stream, radius, view);
 }

@@ -2079,18 +2079,6 @@ static TileGrid make_grid(int S, int row0, int row1, int row_cycle = 1)
     return g;
 }
 
-// Regions of a workspace, carved front to back; every region starts on a 256-byte boundary.  base == nullptr: size query.
-struct Bump {
-    char *base;
-    size_t used;
-    template <typename T> T *take(size_t count)
-    {
-        T *r = base ? reinterpret_cast<T *>(base + used) : nullptr;
-        used += align_up(count * sizeof(T), 256);
-        return r;
-    }
-};
-
 // The layout is sized for the full image (a row band uses a prefix of every region) and is a function of the arguments and
 // DSS_OPT_LEAN_WORKSPACE alone.  ws == nullptr: size query (count_bytes, bytes).
 static FwdWorkspace carve_fwd(void *ws, int N, int64_t P, int S, bool with_records = false)

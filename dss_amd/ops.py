@@ -960,18 +960,22 @@ def camera_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_cloud
     return gM, gV
 
 
+def _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud):
+    """What the kNN entries share: the library, the three checked tensors, N, P and the device."""
+    lib = _lib.load()
+    points = _lib.require_gpu(points, "points", _f32)
+    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
+    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    return lib, points, first, num, first.shape[0], points.shape[0], points.device
+
+
 def knn_kth_sqdist(points, cloud_to_packed_first_idx, num_points_per_cloud, K: int = 7, radius=None):
     """K-th smallest squared distance of every point to its own cloud (self included) -> (P,).
     Exact grid search in HIP; replaces frnn.frnn_grid_points / pytorch3d.ops.knn_points for the
     variance-scale statistic (rasterizer.py:310-321, 366-383).  ``radius`` > 0 (``dss_knn_kth_sqdist_radius``): the
     fixed-radius semantics of the reference's DEFAULT search, ``frnn_grid_points(K, r = frnn_radius = 0.2)`` -- the largest of
     the K - 1 neighbour distances that lie within ``radius``, -1 for a point that has no neighbour there."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
-    dev = points.device
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N, P = first.shape[0], points.shape[0]
+    lib, points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
     with torch.cuda.device(dev):
         out = torch.empty((P,), dtype=_f32, device=dev)
         ws = _lib.workspace(dev, lib.dss_knn_workspace(N, P))
@@ -989,12 +993,7 @@ def knn_points(points, cloud_to_packed_first_idx, num_points_per_cloud, K: int):
     """Self kNN of packed clouds -> (dists (P,K) squared, idx (P,K) int64 cloud-local), ascending, the point itself
     first, zero-padded for clouds with fewer than K points: the packed form of
     ``pytorch3d.ops.knn_points(p, p, lengths, lengths, K)`` used by the regularisers (losses.py:157-180)."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
-    dev = points.device
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N, P = first.shape[0], points.shape[0]
+    lib, points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
     with torch.cuda.device(dev):
         dists = torch.empty((P, int(K)), dtype=_f32, device=dev)
         idx = torch.empty((P, int(K)), dtype=_i64, device=dev)
@@ -1059,15 +1058,11 @@ def knn_kth_sqdist_view(points, cloud_to_packed_first_idx, num_points_per_cloud,
     one cloud, N cameras -> (N, P) (row c: among the points camera c keeps; 0 for the ones it drops); else cloud n belongs to
     camera n -> (P,).  Packed slots outside every cloud (before ``first_idx[0]``, between clouds, behind the last one) are 0,
     in every row."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
-    dev = points.device
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    V =_lib.require_gpu(V, "V", _f32)
+    lib, points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
+    V = _lib.require_gpu(V, "V", _f32)
     znear = _lib.require_gpu(znear, "znear", _f32)
     zfar = _lib.require_gpu(zfar, "zfar", _f32)
-    N, P, n_cams = first.shape[0], points.shape[0], V.shape[0]
+    n_cams = V.shape[0]
     with torch.cuda.device(dev):
         out = torch.empty((n_cams, P) if shared_cloud else (P,), dtype=_f32, device=dev)
         ws = _lib.workspace(dev, lib.dss_knn_workspace(N, P))

@@ -13,8 +13,8 @@ under DSS_OPT_KNN_QUERY = 0, 1, 2, 3 each; "straddle" = the two sizes of the sha
   skip structure off / on (P >= 65536)                          matrix P = 65535 | P >= 65536; option 3 turns it off
   dense_flag down / up with the structure built                 matrix even, lumpy | clustered
   cooperative query, no skip / skip instance                    matrix P = 65535 | 65536 .. 120000 (option 0), all (option 1)
-  one-thread query alone (ROLE 0)                               matrix option 2 at P = 65535, option 3 at P >= 120001
-  one-thread ROLE 1 + cooperative ROLE 2 pair                   matrix P >= 120001 (option 0), P >= 65536 (option 2)
+  one-thread query alone (role 0)                               matrix option 2 at P = 65535, option 3 at P >= 120001
+  one-thread role 1 + cooperative role 2 pair                   matrix P >= 120001 (option 0), P >= 65536 (option 2)
   one-thread query with 64 / 256 threads per workgroup          matrix P <= 131072 | P = 131073
   K-th distance instances <8> / <16>                            matrix K = 1, 7, 8 | 9, 16
   full lists <8> / <12> / <16> / one-thread <40>                matrix K = 8 | 12 | 16 | 17, 40
@@ -137,7 +137,7 @@ def test_camera_whose_drops_share_a_wavefront_with_the_previous_clouds_is_flagge
     """One cloud per camera; camera 0 drops the last 5 points of cloud 0 and camera 1 exactly the first 12 of cloud 1: all of
     camera 1's dropped points sit in the wavefront of knn_fill_kernel that also holds dropped points of cloud 0 at lower
     lanes.  Camera 1's "drops points" flag must still go up, or every query of cloud 1 gets the statistic of the WHOLE
-    cloud.  (1000, 1500): small build, cooperative query; (99790, 99790): large build, one-thread query + the ROLE pair."""
+    cloud.  (1000, 1500): small build, cooperative query; (99790, 99790): large build, one-thread query + the role pair."""
     assert sizes[0] % 64 != 0 and 64 - sizes[0] % 64 >= 12
     clouds, V, znear, zfar = _straddle_scene(sizes, (5, 12))
     assert _hidden_drop_count(clouds[1], V[1], znear[1], zfar[1]) >= 10    # the scene shows the defect
