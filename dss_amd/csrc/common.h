@@ -8,29 +8,11 @@
 #define DSS_WAVE 64
 #define DSS_TILE 8           // screen tile side in pixels (one 256-thread workgroup per tile)
 #define DSS_TILE_PIX (DSS_TILE * DSS_TILE)
+#include "tile_rect.h"   // pix_to_ndc, NdcMap, ndc_index_range, TileGrid, splat_tile_rect
 
 namespace dss {
 
 void set_error(const char *fmt, ...);
-
-// Pixel index -> NDC centre.  Same expression, same fp32 rounding as PixToNdc
-// (reference rasterization_utils.cuh:8-11): -1 + (2*i + 1.0f) / S.
-__device__ __forceinline__ float pix_to_ndc(int i, int S) { return -1 + (2 * i + 1.0f) / S; }
-
-// Same value as pix_to_ndc for every S: when S is a power of two, multiplying by the exactly
-// representable 1/S rounds identically to the division (one v_mul instead of a ~10-instruction
-// IEEE divide in inner loops); otherwise fall back to the division.  `pow2` is wave-uniform.
-struct NdcMap {
-    int S;
-    float invS;
-    bool pow2;
-    __device__ __forceinline__ explicit NdcMap(int S_) : S(S_), invS(1.0f / (float)S_), pow2((S_ & (S_ - 1)) == 0) {}
-    __device__ __forceinline__ float operator()(int i) const
-    {
-        const float t = 2 * i + 1.0f;
-        return pow2 ? -1 + t * invS : -1 + t / S;
-    }
-};
 
 // Cloud that owns packed point p (N is small; clouds are disjoint index ranges).
 __device__ __forceinline__ int find_cloud(int64_t p, const int64_t *__restrict__ first_idx,
@@ -41,24 +23,6 @@ __device__ __forceinline__ int find_cloud(int64_t p, const int64_t *__restrict__
         if (p >= f && p < f + num_pts[n]) return n;
     }
     return -1;
-}
-
-// Range [lo, hi] of NDC pixel indices i in [0,S) whose centre may satisfy |ndc(i) - x| <= r.
-// Conservative (one pixel of slack each side); the exact fp32 test runs later per pixel.
-// Non-finite inputs select the whole axis.  Returns false if the range is empty.
-__device__ __forceinline__ bool ndc_index_range(float x, float r, int S, int &lo, int &hi)
-{
-    const float flo = ((x - r + 1.0f) * S - 1.0f) * 0.5f;
-    const float fhi = ((x + r + 1.0f) * S - 1.0f) * 0.5f;
-    lo = 0;
-    hi = S - 1;
-    if (flo == flo && fhi == fhi) {  // not NaN
-        if (fhi < -2.0f || flo > (float)S + 1.0f) return false;
-        const float a = fmaxf(flo, -2.0f), b = fminf(fhi, (float)S + 1.0f);
-        lo = max(0, (int)floorf(a) - 1);
-        hi = min(S - 1, (int)ceilf(b) + 1);
-    }
-    return lo <= hi;
 }
 
 // Wave-wide sum without LDS traffic: `__shfl_xor` lowers to ds_bpermute_b32 (an LDS round trip per

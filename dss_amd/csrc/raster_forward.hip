@@ -144,20 +144,6 @@ __device__ __forceinline__ void spill_begin(const Spill sp)
     sp.fail[3] = sp.fail[2];
 }
 
-struct TileGrid {
-    int S;        // image side
-    int row0;     // first image row of the band
-    int rows;     // rows in the band (band-local rows: the band tensors have this many rows)
-    int tiles_x;  // tiles per band row
-    int tiles_y;  // tile rows in the band
-    int tshift;   // log2 of the image-row distance of two consecutive band tile rows: 3 for a contiguous band; 3 + log2(c)
-                  // for a tile-row-CYCLIC band (multi-GPU: a rank owns every c-th 8-row tile row starting at row0, so that
-                  // every rank gets the same mix of dense and empty screen regions).  Band-local row l <-> image row
-                  // row0 + ((l >> 3) << tshift) + (l & 7).
-};
-// first image row of band tile row ty
-__host__ __device__ __forceinline__ int tile_row0(const TileGrid &g, int ty) { return g.row0 + (ty << g.tshift); }
-
 // Super-block (i, j) of camera n goes to XCD (i + 3 j + 5 n) mod 8: neighbours in a row differ by 1, in a column by 3, so
 // any compact screen region is spread evenly over the XCDs (the first version dealt the 64x64-pixel super-blocks of a
 // 512^2 image by COLUMN: a centred object then ran on three of the eight XCDs).
@@ -174,56 +160,6 @@ __device__ __forceinline__ int queue_of(int n, int tx, int ty, const TileGrid &g
 {
     const int xcd = ((tx >> DSS_SB_SHIFT) + 3 * (ty >> DSS_SB_SHIFT) + 5 * n) & 7;
     return xcd + 8 * (((ty & 1) << 1) | (tx & 1));
-}
-
-// ---------------------------------------------------------------------------------------------
-// Splat -> tile rectangle (band-local tile coordinates).  Image column c <-> NDC index S-1-c.
-// The rectangle is exact: it is the set of tiles containing at least one pixel whose centre
-// passes both axis tests |dx|<=rx and |dy|<=ry (the Q test can only remove pixels).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool splat_tile_rect(float px, float py, float pz, float rx, float ry,
-                                                const TileGrid g, int &tx0, int &tx1, int &ty0, int &ty1)
-{
-    if (pz < 0) return false;  // rasterize_points.cu:79-80
-    int xlo, xhi, ylo, yhi;
-    if (!ndc_index_range(px, rx, g.S, xlo, xhi)) return false;
-    if (!ndc_index_range(py, ry, g.S, ylo, yhi)) return false;
-    // tighten with the exact per-pixel predicate (monotone in the pixel index).  The loops run 1-3 times; they
-    // must stay rolled and free of the IEEE divide of the non-power-of-two pixel map (unrolled eightfold with the
-    // divide inlined they were 1100 instructions and 8.5k of the binning kernel's 30k cycles per wavefront).
-    const NdcMap ndc(g.S);
-    // (the empty asm keeps the optimiser from turning each search into an eightfold-unrolled batch evaluation)
-#define DSS_TIGHTEN(NDC_EXPR)                                                              \
-    while (xlo <= xhi && fabsf(NDC_EXPR(xlo) - px) > rx) { ++xlo; asm volatile("" : "+v"(xlo)); } \
-    while (xhi >= xlo && fabsf(NDC_EXPR(xhi) - px) > rx) { --xhi; asm volatile("" : "+v"(xhi)); } \
-    while (ylo <= yhi && fabsf(NDC_EXPR(ylo) - py) > ry) { ++ylo; asm volatile("" : "+v"(ylo)); } \
-    while (yhi >= ylo && fabsf(NDC_EXPR(yhi) - py) > ry) { --yhi; asm volatile("" : "+v"(yhi)); }
-    if (ndc.pow2) {  // uniform
-        const float inv = ndc.invS;
-#define DSS_NDC_POW2(i) (-1 + (2 * (i) + 1.0f) * inv)
-        DSS_TIGHTEN(DSS_NDC_POW2)
-#undef DSS_NDC_POW2
-    } else {
-#define DSS_NDC_DIV(i) pix_to_ndc((i), g.S)
-        DSS_TIGHTEN(DSS_NDC_DIV)
-#undef DSS_NDC_DIV
-    }
-#undef DSS_TIGHTEN
-    if (xlo > xhi || ylo > yhi) return false;
-    const int c0 = g.S - 1 - xhi, c1 = g.S - 1 - xlo;
-    int r0 = g.S - 1 - yhi, r1 = g.S - 1 - ylo;
-    // band tile rows whose 8 image rows [R, R + 7], R = row0 + (ty << tshift), meet [r0, r1] (contiguous band, tshift = 3:
-    // ty = (r - row0) / 8 as before; the last tile row of a band may be short: rows beyond g.rows are never stored)
-    r0 = max(r0, g.row0);
-    r1 = min(r1, tile_row0(g, g.tiles_y - 1) + (g.rows - 1 - (g.tiles_y - 1) * DSS_TILE));   // last image row of the band
-    if (r0 > r1) return false;
-    tx0 = c0 / DSS_TILE;
-    tx1 = c1 / DSS_TILE;
-    const int step = 1 << g.tshift;
-    ty0 = (r0 - g.row0 - (DSS_TILE - 1) + step - 1) >> g.tshift;   // ceil((r0 - row0 - 7) / step), numerator + step - 1 >= 0
-    ty0 = max(ty0, 0);
-    ty1 = min((r1 - g.row0) >> g.tshift, g.tiles_y - 1);
-    return ty0 <= ty1;
 }
 
 // First entry of one of the tile's sub-lists: claim the tile (at most DSS_SUB threads per tile get here, exactly one
@@ -345,6 +281,55 @@ __global__ __launch_bounds__(256) void bin_kernel(
               lists, cap, tq, sp);
 }
 
+// Cloud n that owns EVERY packed point of [pf, pl] (all three the same in every lane), or -1: uniform loads only.
+__device__ __forceinline__ int find_cloud_span(int64_t pf, int64_t pl, const int64_t *first_idx, const int64_t *num_pts, int N)
+{
+    for (int n = 0; n < N; ++n) {
+        const int64_t f = uniform_load(first_idx + n);
+        if (pf >= f && pl < f + uniform_load(num_pts + n)) return n;
+    }
+    return -1;
+}
+
+// The 64 consecutive points of a wavefront lie in ONE cloud unless the wavefront straddles a cloud boundary (never with one
+// cloud, N - 1 wavefronts otherwise).  Then the cloud, its first index, its two matrices, its depth range and its h are the
+// same in every lane: they come through uniform (scalar) loads, one request per wavefront (the per-lane form is ~40 vector
+// loads of wave-uniform values, the matrix behind the depth test at that), and they are requested TOGETHER with the point's own
+// world / normal / feature rows instead of one round trip (the lookup) ahead of them: where row p of the world arrays exists
+// whatever the lookup says (clouds that are not shared: Pw == P; a single shared cloud: P == N Pw == Pw, include/dss_hip.h)
+// it is requested before the lookup returns, and requested again in the one case in which it was not the point's row (a
+// single shared cloud that does not start at 0).
+// A straddling wavefront takes the per-lane path (find_cloud + setup_point_compute).  Returns the point's cloud, or -1.
+__device__ __forceinline__ int setup_point_wave(const SetupArgs &A, int64_t p, SetupVals &v)
+{
+    const int64_t pf = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(p >> 32)) << 32) |
+                                 (uint32_t)__builtin_amdgcn_readfirstlane((int)p));   // (lane 0: the lanes beyond P have left)
+    const int64_t pl = min(pf + (DSS_WAVE - 1), A.P - 1);
+    SetupIn in = {};
+    setup_load_features(A, p, in);
+    const bool early = !A.shared || A.N == 1;
+    if (early) setup_load_world(A, p, in);
+    const int ns = A.N == 1 ? 0 : find_cloud_span(pf, pl, A.first_idx, A.num_pts, A.N);
+    const int nc = max(ns, 0);
+    const int64_t first = uniform_load(A.first_idx + nc), count = uniform_load(A.num_pts + nc);
+    CamWave cam = load_cam_wave(A, nc);
+    // One cloud: every uniform load above is in flight by now, behind the point's own rows: one wait for all of them.  More
+    // clouds: NOT overlapped like that -- find_cloud_span is a chain of dependent uniform loads (one round trip per cloud
+    // tried), the camera loads wait for its result, and the rows of a SHARED cloud are requested only after this wait.
+    cam_to_lanes(cam);
+    if (ns >= 0 && pf >= first && pl < first + count) {
+        FT_MARK_S(1);
+        const int64_t wi = A.shared ? p - first : p;
+        if (A.shared && (!early || first != 0)) setup_load_world(A, wi, in);
+        v = setup_point_arith(A, p, wi, true, cam, in);
+        return nc;
+    }
+    const int n = find_cloud(p, A.first_idx, A.num_pts, A.N);
+    FT_MARK_S(1);
+    v = setup_point_compute(A, p, n);
+    return n;
+}
+
 // dss_render_forward: per-point setup (culling + projection + EWA terms) fused with the binning --
 // the screen record goes from registers straight into the tile lists.
 // BAND_ONLY (DSS_WS_BAND_OUTPUTS, multi-GPU): a splat whose tile rectangle misses the rank's band writes its screen position,
@@ -359,11 +344,9 @@ __global__ __launch_bounds__(256) void setup_bin_kernel(const SetupArgs A, TileG
     if (p >= A.P) return;
     if (visible_to_clear) visible_to_clear[p] = 0;
     FT_MARK_S(0);
-    const int n = find_cloud(p, A.first_idx, A.num_pts, A.N);
-    FT_MARK_S(1);
-    float px, py, pz, rx, ry;
+    SetupVals v;
+    const int n = setup_point_wave(A, p, v);
     if (BAND_ONLY) {
-        const SetupVals v = setup_point_compute(A, p, n);
         int tx0, tx1, ty0, ty1;
         const bool reach = n >= 0 && splat_tile_rect(v.sx, v.sy, v.sz, v.rx, v.ry, g, tx0, tx1, ty0, ty1);
         setup_point_store(A, p, v, reach);
@@ -371,19 +354,14 @@ __global__ __launch_bounds__(256) void setup_bin_kernel(const SetupArgs A, TileG
         if (reach) bin_rect(p, n, tx0, tx1, ty0, ty1, g, counts, lists, cap, tq, sp);   // (the rectangle is computed once)
         FT_MARK_S(5);
         return;
-    } else {
-#ifdef DSS_FINE_TIMING
-        const SetupVals v = setup_point_compute(A, p, n);
-        asm volatile("" ::"v"(v.rx), "v"(v.ry), "v"(v.sc), "v"(v.ea));   // (the arithmetic has finished)
-        FT_MARK_S(6);
-        setup_point_store(A, p, v);
-        px = v.sx; py = v.sy; pz = v.sz; rx = v.rx; ry = v.ry;
-#else
-        setup_point(A, p, n, px, py, pz, rx, ry);
-#endif
     }
+#ifdef DSS_FINE_TIMING
+    asm volatile("" ::"v"(v.rx), "v"(v.ry), "v"(v.sc), "v"(v.ea));   // (the arithmetic has finished)
+    FT_MARK_S(6);
+#endif
+    setup_point_store(A, p, v);
     FT_MARK_S(2);
-    bin_point(p, n, px, py, pz, rx, ry, g, counts, lists, cap, tq, sp);
+    bin_point(p, n, v.sx, v.sy, v.sz, v.rx, v.ry, g, counts, lists, cap, tq, sp);
     FT_MARK_S(5);
 }
 

@@ -39,42 +39,113 @@ struct SetupVals {
     uint8_t ok;
 };
 
-// Setup of packed point p of cloud n (n < 0: unowned point -> culled): the arithmetic alone.
-__device__ __forceinline__ SetupVals setup_point_compute(const SetupArgs &A, int64_t p, int n)
+// Where the setup takes the values of its camera / cloud from.  CamLane: cloud n may differ from lane to lane, every value is
+// a load through the lane's own n at the place of its use.  CamWave (setup_bin_kernel): the wavefront's 64 points lie in one
+// cloud, the values were fetched once per wavefront by uniform (scalar) loads.
+struct CamLane {
+    const float *mp, *vp, *zn, *zf, *hc;
+    int n;
+    __device__ __forceinline__ CamLane(const float *M, const float *V, const float *znear, const float *zfar, const float *h_cloud, int n_)
+        : mp(M + 16 * n_), vp(V + 16 * n_), zn(znear), zf(zfar), hc(h_cloud), n(n_) {}
+    __device__ __forceinline__ float m(int j) const { return mp[j]; }
+    __device__ __forceinline__ float v(int j) const { return vp[j]; }
+    __device__ __forceinline__ float znear() const { return zn[n]; }
+    __device__ __forceinline__ float zfar() const { return zf[n]; }
+    __device__ __forceinline__ float h_cloud() const { return hc[n]; }
+};
+struct CamWave {
+    float mv[16];
+    float v2, v6, v10, v14, zn, zf, hc;
+    __device__ __forceinline__ float m(int j) const { return mv[j]; }
+    __device__ __forceinline__ float v(int j) const { return j == 2 ? v2 : j == 6 ? v6 : j == 10 ? v10 : v14; }
+    __device__ __forceinline__ float znear() const { return zn; }
+    __device__ __forceinline__ float zfar() const { return zf; }
+    __device__ __forceinline__ float h_cloud() const { return hc; }
+};
+// A load that the compiler may issue as a scalar (uniform) load: p must be the same in every lane and the memory behind it
+// must not be written during the launch.
+template <typename T> __device__ __forceinline__ T uniform_load(const T *p)
+{
+    return *(const __attribute__((address_space(4))) T *)p;
+}
+// (h_cloud is read only where the arithmetic uses it: not in anisotropic mode and not next to h_point, where the array behind a
+// non-null pointer need not hold N values, include/dss_hip.h)
+__device__ __forceinline__ CamWave load_cam_wave(const SetupArgs &A, int n)
+{
+    CamWave c;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) c.mv[j] = uniform_load(A.M + 16 * n + j);
+    c.v2 = uniform_load(A.V + 16 * n + 2); c.v6 = uniform_load(A.V + 16 * n + 6);
+    c.v10 = uniform_load(A.V + 16 * n + 10); c.v14 = uniform_load(A.V + 16 * n + 14);
+    c.zn = uniform_load(A.znear + n); c.zf = uniform_load(A.zfar + n);
+    c.hc = (A.h_cloud && !A.h_point && !A.vr6) ? uniform_load(A.h_cloud + n) : 0.0f;
+    return c;
+}
+// The 23 values move from scalar to vector registers once they have arrived: next to the kernel's ~75 dwords of arguments they
+// do not fit the scalar file (the compiler then reuses one register for several loads, each with a wait of its own), and a
+// VALU instruction reads one scalar operand at most.
+__device__ __forceinline__ float lanes_of(float s)
+{
+    float v;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
+    return v;
+}
+__device__ __forceinline__ void cam_to_lanes(CamWave &c)
+{
+#pragma unroll
+    for (int j = 0; j < 16; ++j) c.mv[j] = lanes_of(c.mv[j]);
+    c.v2 = lanes_of(c.v2); c.v6 = lanes_of(c.v6); c.v10 = lanes_of(c.v10); c.v14 = lanes_of(c.v14);
+    c.zn = lanes_of(c.zn); c.zf = lanes_of(c.zf); c.hc = lanes_of(c.hc);
+}
+
+// What the setup reads of its point before the arithmetic starts.
+struct SetupIn {
+    float ph0, ph1, ph2, n0, n1, n2;   // world position, cloud normal (row wi of world / normals)
+    float fr0, fr1, fr2;               // the features that ride in the packed record (0 without records)
+};
+__device__ __forceinline__ void setup_load_features(const SetupArgs &A, int64_t p, SetupIn &in)
+{
+    in.fr0 = in.fr1 = in.fr2 = 0.f;
+    if (A.rec) {
+        const float *f = A.feat + 3 * (size_t)p;
+        in.fr0 = f[0]; in.fr1 = f[1]; in.fr2 = f[2];
+    }
+}
+__device__ __forceinline__ void setup_load_world(const SetupArgs &A, int64_t wi, SetupIn &in)
+{
+    in.ph0 = A.world[3 * wi]; in.ph1 = A.world[3 * wi + 1]; in.ph2 = A.world[3 * wi + 2];
+    in.n0 = A.normals[3 * wi]; in.n1 = A.normals[3 * wi + 1]; in.n2 = A.normals[3 * wi + 2];
+}
+
+// Setup of packed point p = row wi of the world arrays, `owned` by a cloud whose camera is `cam` (not owned -> culled): the
+// arithmetic alone.
+template <class Cam>
+__device__ __forceinline__ SetupVals setup_point_arith(const SetupArgs &A, int64_t p, int64_t wi, bool owned, const Cam &cam,
+                                                       const SetupIn &in)
 {
     float sx = 0.f, sy = 0.f, sz = -1.0f, ea = 1.f, eb = 0.f, ec = 1.f, rx = 0.f, ry = 0.f, sc = 0.f;
     uint8_t ok = 0;
-    // the features that ride in the packed record: requested FIRST (their address only depends on p).  Left next to the
-    // record stores at the end of the function the load sat behind every output store (the compiler may not move it above
-    // stores that could alias) and added one cold memory round trip to the binning kernel's dependent chain (-0.6 us per step).
-    float fr0 = 0.f, fr1 = 0.f, fr2 = 0.f;
-    if (A.rec) {
-        const float *f = A.feat + 3 * (size_t)p;
-        fr0 = f[0]; fr1 = f[1]; fr2 = f[2];
-    }
-    if (n >= 0) {
-        const int64_t wi = A.shared ? (p - A.first_idx[n]) : p;
-        const float *m = A.M + 16 * n;
-        const float *v = A.V + 16 * n;
-        const float ph0 = A.world[3 * wi], ph1 = A.world[3 * wi + 1], ph2 = A.world[3 * wi + 2], ph3 = 1.0f;
-        const float n0 = A.normals[3 * wi], n1 = A.normals[3 * wi + 1], n2 = A.normals[3 * wi + 2];
+    const float fr0 = in.fr0, fr1 = in.fr1, fr2 = in.fr2;
+    if (owned) {
+        const float ph0 = in.ph0, ph1 = in.ph1, ph2 = in.ph2, ph3 = 1.0f;
+        const float n0 = in.n0, n1 = in.n1, n2 = in.n2;
 #ifdef DSS_FINE_TIMING
         asm volatile("" ::"v"(ph0), "v"(ph2), "v"(n0), "v"(n2));   // (the inputs have arrived)
         DSS_SETUP_MARK(7);
 #endif
-        const float zview = ph0 * v[2] + ph1 * v[6] + ph2 * v[10] + ph3 * v[14];
+        const float zview = ph0 * cam.v(2) + ph1 * cam.v(6) + ph2 * cam.v(10) + ph3 * cam.v(14);
         // _filter_points_with_invalid_depth, rasterizer.py:183-217
-        ok = (zview >= A.znear[n]) && (zview <= A.zfar[n]);
+        ok = (zview >= cam.znear()) && (zview <= cam.zfar());
         if (A.backface) {
             // _filter_backface_points, rasterizer.py:148-181: keep view-space normal z < 0.
             // transform_normals uses the inverse-transpose of the rotation block; R is orthonormal.
-            const float nz = n0 * v[2] + n1 * v[6] + n2 * v[10];
+            const float nz = n0 * cam.v(2) + n1 * cam.v(6) + n2 * cam.v(10);
             ok = ok && (nz < 0);
         }
         if (ok) {
             float clip[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) clip[j] = ph0 * m[j] + ph1 * m[4 + j] + ph2 * m[8 + j] + ph3 * m[12 + j];
+            for (int j = 0; j < 4; ++j) clip[j] = ph0 * cam.m(j) + ph1 * cam.m(4 + j) + ph2 * cam.m(8 + j) + ph3 * cam.m(12 + j);
             const float w = clip[3];
             sx = clip[0] / w;
             sy = clip[1] / w;
@@ -85,7 +156,7 @@ __device__ __forceinline__ SetupVals setup_point_compute(const SetupArgs &A, int
             for (int i = 0; i < 3; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    WJ[i][j] = m[i * 4 + j] * (1.0f / dw) + m[i * 4 + 3] * (-1.0f / dw2 * clip[j]);
+                    WJ[i][j] = cam.m(i * 4 + j) * (1.0f / dw) + cam.m(i * 4 + 3) * (-1.0f / dw2 * clip[j]);
             // anisotropic mode (rasterizer.py:256-291): Vrk is an input and the tangent frame of det(Sk WJk) is
             // the PCA frame, whose normal replaces the cloud normal below (culling above used the cloud normal)
             const bool aniso = A.vr6 != nullptr;
@@ -93,7 +164,7 @@ __device__ __forceinline__ SetupVals setup_point_compute(const SetupArgs &A, int
                         f2 = aniso ? A.frame_n[3 * wi + 2] : n2;
             // h_point AND h_cloud given: h_point holds one value per PACKED point (a shared cloud whose cameras cull differently:
             // the reference evaluates the isotropic scale on each camera's filtered cloud, rasterizer.py:344-402)
-            const float hh = aniso ? 0.0f : (A.h_point ? A.h_point[A.h_cloud ? p : wi] : A.h_cloud[n]);
+            const float hh = aniso ? 0.0f : (A.h_point ? A.h_point[A.h_cloud ? p : wi] : cam.h_cloud());
             // Sk^T Sk = I - n^ n^^T with the NORMALISED normal (rasterizer.py:337-341); zero normal -> 0
             const float nlen = sqrtf(f0 * f0 + f1 * f1 + f2 * f2);
             const float nden = nlen > 1e-12f ? nlen : 1e-12f;
@@ -146,6 +217,22 @@ __device__ __forceinline__ SetupVals setup_point_compute(const SetupArgs &A, int
     v.sx = sx; v.sy = sy; v.sz = sz; v.ea = ea; v.eb = eb; v.ec = ec; v.rx = rx; v.ry = ry; v.sc = sc;
     v.fr0 = fr0; v.fr1 = fr1; v.fr2 = fr2; v.ok = ok;
     return v;
+}
+
+// Setup of packed point p of cloud n (n < 0: unowned point -> culled), n any value per lane.
+__device__ __forceinline__ SetupVals setup_point_compute(const SetupArgs &A, int64_t p, int n)
+{
+    // the features that ride in the packed record: requested FIRST (their address only depends on p).  Left next to the
+    // record stores at the end of the function the load sat behind every output store (the compiler may not move it above
+    // stores that could alias) and added one cold memory round trip to the binning kernel's dependent chain (-0.6 us per step).
+    SetupIn in;
+    setup_load_features(A, p, in);
+    int64_t wi = p;
+    if (n >= 0) {
+        wi = A.shared ? (p - A.first_idx[n]) : p;
+        setup_load_world(A, wi, in);
+    }
+    return setup_point_arith(A, p, wi, n >= 0, CamLane(A.M, A.V, A.znear, A.zfar, A.h_cloud, n), in);
 }
 
 // one thread writes the outputs of its point.  full = false (DSS_WS_BAND_OUTPUTS, a splat that cannot reach the rank's row
