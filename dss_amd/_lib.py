@@ -105,6 +105,9 @@ SIGNATURES = {
     "dss_camera_backward": (_c_int, [_c_vp] * 5 + [_c_int, _c_i64, _c_int, _c_vp, _c_vp, _c_f32, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "dss_phong_backward_camera": (_c_int, [_c_vp] * 6 + [_c_int, _c_i64, _c_int] + [_c_vp] * 4 + [_c_int, _c_int, _c_vp, _c_f32,
                                                                                                  _c_vp, _c_vp, _c_sz, _c_vp]),
+    "dss_phong_backward_lights_workspace": (_c_sz, [_c_int, _c_i64, _c_int]),
+    "dss_phong_backward_lights": (_c_int, [_c_vp] * 6 + [_c_int, _c_i64, _c_int] + [_c_vp] * 4 + [_c_int, _c_int, _c_vp, _c_f32]
+                                  + [_c_vp] * 4 + [_c_vp, _c_sz, _c_vp]),
     "dss_blend_backward": (_c_int, [_c_vp] * 10 + [_c_int, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "dss_blend_backward_scatter": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [_c_i64, _c_vp, _c_vp]),
 }

@@ -12,12 +12,18 @@
 //                                  grad_V[n][:, 2] = sum_p x gz              (the other columns of grad_V are 0)
 //   dss_phong_backward_camera  grad_cam[n] = + sum_p gw(n, p), gw = the gradient of w = camera - x that phong_kernel<true>
 //                              (shading.hip) subtracts from the point's gradient.
+//   dss_phong_backward_lights  the same shading differentiated w.r.t. the LIGHTS, which the reference keeps on the tape
+//                              (DSS/core/texture.py:25-63, :118-122; DSS/core/lighting.py:10-77, :80-172, :175-302):
+//                                  grad_ambient[n]     = sum_p g c            grad_diffuse[n][l]   = sum_p g c D_l
+//                                  grad_specular[n][l] = sum_p g S_l          grad_light_vec[n][l] = sum_p normalize_backward(u_l, gdv_l)
+//                              in the notation of phong_kernel<true> (g = grad_out, c = rgb of the pair).
 //
-// Both are bitwise reproducible (no atomics) and do not depend on the device they run on: a fixed assignment of
+// All are bitwise reproducible (no atomics) and do not depend on the device they run on: a fixed assignment of
 // (camera, point range) to workgroups that is a function of the sizes only (`reduce_plan`), per-thread fp32 sums over a
 // bounded run of points, a fixed wave tree (DPP) and workgroup tree (LDS), ONE partial per workgroup stored to the
-// workspace, and a second small launch that adds every camera's partials in index order in fp64 and writes fp32.  The
-// launch boundary is the hand-off between the two stages: no flags, no fences, no counters to re-initialise.
+// workspace, and a second small launch that adds the partials of every row (a camera, or a (camera, light)) in index order
+// in fp64 and writes fp32.  The launch boundary is the hand-off between the two stages: no flags, no fences, no counters
+// to re-initialise.
 #include "common.h"
 
 namespace dss {
@@ -219,19 +225,107 @@ __global__ __launch_bounds__(RB_BLOCK) void phong_camera_partial_kernel(const Ph
     block_sum_store<4>(acc, partials + ((size_t)n * gridDim.x + blockIdx.x) * 4);
 }
 
-// Stage 2 of both: workgroup n adds the `blocks` partials (W floats each) of camera n in fp64 -- RB_BLOCK / W contiguous
-// runs of the index range in parallel, each in index order, then the runs in order -- and writes fp32.
-//   CAMERA: W = 16 -> grad_M[n], grad_V[n] (4,4) fully written, zeros included;  otherwise W = 4 -> grad_cam[n] (3).
-template <int W, bool CAMERA>
-__global__ __launch_bounds__(RB_BLOCK) void sum_partials_kernel(const float *__restrict__ partials, int blocks,
-                                                                float *__restrict__ out0, float *__restrict__ out1)
+// The 16-float slot of one (camera, light) of dss_phong_backward_lights: [g_kd(3), g_ks(3), g_vec(3), g_amb(3), pad(4)];
+// g_amb is carried by light 0 only (zeros in the other slots).  L == 0: one slot per camera with the ambient term alone.
+constexpr int LS_W = 16, LS_KD = 0, LS_KS = 3, LS_VEC = 6, LS_AMB = 9;
+
+struct PhongLightArgs {
+    const float *grad_out, *world, *normals, *rgb;   // (P,3), (Pw,3), (Pw,3), (P,3)
+    const int64_t *first_idx, *num_pts;
+    int shared, L, point_lights;
+    int64_t Pw, P;
+    const float *kd, *ks, *lvec, *cam;               // (N,L,3), (N,L,3), (N,L,3), (N,3)
+    float shininess;
+};
+
+// Stage 1 of dss_phong_backward_lights: workgroup (b, n, l) sums ONE light's terms over its share of camera n's pairs, one
+// pair per lane and sweep; gridDim.z = max(L, 1) and its partial lands in slot n * gridDim.z + l, so that stage 2 sees the
+// slots as rows.  L is a launch dimension, not a template argument, so the cost per thread does not depend on it: 12 live
+// fp32 accumulators (the pad of the slot is a constant zero) next to the ~40 values of one pair and one light -- 69 VGPRs
+// as compiled for gfx950, no scratch -- and 64 floats of LDS per WORKGROUP (block_sum_store<16>), a quarter of a float per
+// thread.  The price is that every light re-reads the pair (48 bytes) and re-normalises n^ and v^; accumulating all lights
+// in one pass would need 9 L + 3 accumulators per thread, i.e. either a kernel per L or 16 L floats of LDS per thread.
+// The pair's D, S and gdv (d loss / d d^) are RESTATED from phong_kernel<true> (shading.hip) operation by operation, like
+// phong_camera_partial_kernel's gv, for the one light of this workgroup: the sums over lights of that kernel (dif, spec, gn,
+// gv) do not reach these outputs.
+__global__ __launch_bounds__(RB_BLOCK) void phong_light_partial_kernel(const PhongLightArgs A, int sweeps,
+                                                                       float *__restrict__ partials)
+{
+    const int n = blockIdx.y, l = blockIdx.z;
+    float acc[LS_W];
+#pragma unroll
+    for (int e = 0; e < LS_W; ++e) acc[e] = 0.f;
+    const int64_t f = A.first_idx[n];
+    const int64_t lo = max(f, (int64_t)0), hi = min(f + A.num_pts[n], A.P);
+    for (int s = 0; s < sweeps; ++s) {
+        const int64_t p = lo + ((int64_t)blockIdx.x * sweeps + s) * RB_BLOCK + threadIdx.x;
+        if (p >= hi) break;
+        const int64_t wi = A.shared ? p - f : p;
+        if (wi >= A.Pw) continue;
+        const float c[3] = {A.rgb[3 * p], A.rgb[3 * p + 1], A.rgb[3 * p + 2]};
+        const float g[3] = {A.grad_out[3 * p], A.grad_out[3 * p + 1], A.grad_out[3 * p + 2]};
+        if (l == 0) {                                           // out = c * (ambient + ...) + ...
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) acc[LS_AMB + ch] += g[ch] * c[ch];
+        }
+        if (A.L == 0) continue;
+        const float x[3] = {A.world[3 * wi], A.world[3 * wi + 1], A.world[3 * wi + 2]};
+        const float m[3] = {A.normals[3 * wi], A.normals[3 * wi + 1], A.normals[3 * wi + 2]};
+        const float mn = cam_safe_norm(m[0], m[1], m[2]);
+        const float nh[3] = {m[0] / mn, m[1] / mn, m[2] / mn};
+        const float w[3] = {A.cam[3 * n] - x[0], A.cam[3 * n + 1] - x[1], A.cam[3 * n + 2] - x[2]};
+        const float wn = cam_safe_norm(w[0], w[1], w[2]);
+        const float v[3] = {w[0] / wn, w[1] / wn, w[2] / wn};
+        const float *lv = A.lvec + ((size_t)n * A.L + l) * 3;
+        const float *kd = A.kd + ((size_t)n * A.L + l) * 3;
+        const float *ks = A.ks + ((size_t)n * A.L + l) * 3;
+        float u[3] = {lv[0], lv[1], lv[2]};
+        if (A.point_lights) { u[0] -= x[0]; u[1] -= x[1]; u[2] -= x[2]; }
+        const float un = cam_safe_norm(u[0], u[1], u[2]);
+        const float d[3] = {u[0] / un, u[1] / un, u[2] / un};
+        const float ca = nh[0] * d[0] + nh[1] * d[1] + nh[2] * d[2];
+        const float r[3] = {-d[0] + 2.0f * (ca * nh[0]), -d[1] + 2.0f * (ca * nh[1]), -d[2] + 2.0f * (ca * nh[2])};
+        const float a0 = v[0] * r[0] + v[1] * r[1] + v[2] * r[2];
+        const bool lit = ca > 0.0f;
+        const float alpha = lit ? fmaxf(a0, 0.0f) : 0.0f;
+        const float D = fmaxf(ca, 0.0f);
+        const float S = powf(alpha, A.shininess);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            acc[LS_KD + ch] += g[ch] * c[ch] * D;               // dif += kd * D, out = c * (... + dif)
+            acc[LS_KS + ch] += g[ch] * S;                       // spec += ks * S
+        }
+        const float gd = g[0] * c[0] * kd[0] + g[1] * c[1] * kd[1] + g[2] * c[2] * kd[2];   // d loss / d D
+        const float gs = g[0] * ks[0] + g[1] * ks[1] + g[2] * ks[2];                        // d loss / d S
+        float gca = lit ? gd : 0.0f;
+        const float ga0 = (lit && a0 > 0.0f) ? gs * A.shininess * powf(alpha, A.shininess - 1.0f) : 0.0f;
+        float gdv[3];  // d loss / d d^
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gdv[i] = -ga0 * v[i];       // r = -d^ + ...
+        const float gr_n = ga0 * (v[0] * nh[0] + v[1] * nh[1] + v[2] * nh[2]);
+        gca += 2.0f * gr_n;                                     // r = ... + 2 ca n^
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gdv[i] += gca * nh[i];
+        float gu[3];
+        cam_normalize_backward(u, gdv, gu);                     // u = location - x, or the direction itself
+#pragma unroll
+        for (int i = 0; i < 3; ++i) acc[LS_VEC + i] += gu[i];
+    }
+    block_sum_store<LS_W>(acc, partials + (((size_t)n * gridDim.z + l) * gridDim.x + blockIdx.x) * LS_W);
+}
+
+// Stage 2 of all three: a workgroup adds the `blocks` partials (W floats each) of row `row` in fp64 -- RB_BLOCK / W contiguous
+// runs of the index range in parallel, each in index order, then the runs in order -- and rounds to fp32 once.
+// -> total[0..W) in LDS, visible to every thread of the workgroup.
+template <int W>
+__device__ __forceinline__ const float *row_total(const float *__restrict__ partials, int blocks, int row)
 {
     constexpr int RUNS = RB_BLOCK / W;
     __shared__ double run_sum[RUNS][W];
     __shared__ float total[W];
-    const int n = blockIdx.x, e = threadIdx.x % W, j = threadIdx.x / W;
+    const int e = threadIdx.x % W, j = threadIdx.x / W;
     const int i0 = (int)((int64_t)blocks * j / RUNS), i1 = (int)((int64_t)blocks * (j + 1) / RUNS);
-    const float *src = partials + (size_t)n * blocks * W;
+    const float *src = partials + (size_t)row * blocks * W;
     double s = 0.0;
     for (int i = i0; i < i1; ++i) s += (double)src[(size_t)i * W + e];
     run_sum[j][e] = s;
@@ -242,6 +336,17 @@ __global__ __launch_bounds__(RB_BLOCK) void sum_partials_kernel(const float *__r
         total[threadIdx.x] = (float)t;
     }
     __syncthreads();
+    return total;
+}
+
+// Stage 2 of the two camera entries: workgroup n = camera n.
+//   CAMERA: W = 16 -> grad_M[n], grad_V[n] (4,4) fully written, zeros included;  otherwise W = 4 -> grad_cam[n] (3).
+template <int W, bool CAMERA>
+__global__ __launch_bounds__(RB_BLOCK) void sum_partials_kernel(const float *__restrict__ partials, int blocks,
+                                                                float *__restrict__ out0, float *__restrict__ out1)
+{
+    const int n = blockIdx.x;
+    const float *total = row_total<W>(partials, blocks, n);
     if (CAMERA) {
         if (threadIdx.x < 16) {
             const int r = threadIdx.x >> 2, c = threadIdx.x & 3;                 // entry [r][c] of both matrices
@@ -250,6 +355,28 @@ __global__ __launch_bounds__(RB_BLOCK) void sum_partials_kernel(const float *__r
         }
     } else if (threadIdx.x < 3) {
         out0[3 * n + threadIdx.x] = total[threadIdx.x];
+    }
+}
+
+// Stage 2 of dss_phong_backward_lights: workgroup n * slots + l = slot (camera n, light l), slots = max(L, 1).  Every
+// non-NULL output entry is written by exactly one thread of one workgroup (blocks == 0: exact zeros).
+__global__ __launch_bounds__(RB_BLOCK) void sum_light_partials_kernel(const float *__restrict__ partials, int blocks, int L,
+                                                                      float *__restrict__ grad_ambient,
+                                                                      float *__restrict__ grad_diffuse,
+                                                                      float *__restrict__ grad_specular,
+                                                                      float *__restrict__ grad_light_vec)
+{
+    const int row = blockIdx.x, slots = max(L, 1);
+    const int n = row / slots, l = row - n * slots;
+    const float *total = row_total<LS_W>(partials, blocks, row);
+    const int e = threadIdx.x;
+    if (e >= 12) return;
+    const int i = e % 3;
+    if (e >= LS_AMB) {
+        if (l == 0 && grad_ambient) grad_ambient[3 * n + i] = total[e];
+    } else if (L > 0) {
+        float *out = e < LS_KS ? grad_diffuse : e < LS_VEC ? grad_specular : grad_light_vec;
+        if (out) out[3 * (size_t)row + i] = total[e];
     }
 }
 
@@ -339,4 +466,55 @@ extern "C" int dss_phong_backward_camera(const float *grad_out, const float *wor
     hipLaunchKernelGGL((sum_partials_kernel<4, false>), dim3((unsigned)N), dim3(RB_BLOCK), 0, as_stream(stream), partials, blocks,
                        grad_cam, nullptr);
     return check_launch("dss_phong_backward_camera");
+}
+
+// One 16-float slot per (camera, light) and workgroup (L == 0: per camera), at most RB_CAP workgroups per camera.
+extern "C" size_t dss_phong_backward_lights_workspace(int N, int64_t P, int L)
+{
+    if (N <= 0 || P < 0 || L < 0) return 0;
+    int64_t per = (P + RB_BLOCK - 1) / RB_BLOCK;                               // >= reduce_plan(Pw).blocks for Pw <= P
+    if (per > RB_CAP) per = RB_CAP;
+    return align_up((size_t)N * (size_t)(L > 0 ? L : 1) * (size_t)per * LS_W * sizeof(float), 256);
+}
+
+extern "C" int dss_phong_backward_lights(const float *grad_out, const float *world, const float *normals, const float *rgb,
+                                         const int64_t *first_idx, const int64_t *num_pts, int N, int64_t Pw, int shared_cloud,
+                                         const float *ambient, const float *diffuse_color, const float *specular_color,
+                                         const float *light_vec, int L, int point_lights, const float *cam_center,
+                                         float shininess, float *grad_ambient, float *grad_diffuse, float *grad_specular,
+                                         float *grad_light_vec, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N <= 0 || N > 65535 || Pw < 0 || L < 0 || L > 65535) {
+        set_error("dss_phong_backward_lights: bad sizes N=%d Pw=%lld L=%d", N, (long long)Pw, L);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (!first_idx || !num_pts || !cam_center ||
+        (Pw > 0 && (!grad_out || !world || !normals || !rgb || !ambient ||
+                    (L > 0 && (!diffuse_color || !specular_color || !light_vec))))) {
+        set_error("dss_phong_backward_lights: NULL tensor pointer");
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    const int64_t P = shared_cloud ? (int64_t)N * Pw : Pw;
+    const ReducePlan pl = reduce_plan(Pw);
+    const int blocks = Pw > 0 ? pl.blocks : 0;
+    const int slots = L > 0 ? L : 1;
+    const size_t need = dss_phong_backward_lights_workspace(N, P, L);   // >= N * slots * blocks * 16 floats
+    if (!workspace || workspace_bytes < need) {
+        set_error("dss_phong_backward_lights: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    float *partials = static_cast<float *>(workspace);
+    if (blocks > 0) {
+        PhongLightArgs A;
+        A.grad_out = grad_out; A.world = world; A.normals = normals; A.rgb = rgb; A.first_idx = first_idx; A.num_pts = num_pts;
+        A.shared = shared_cloud; A.L = L; A.point_lights = point_lights; A.Pw = Pw; A.P = P; A.kd = diffuse_color;
+        A.ks = specular_color; A.lvec = light_vec; A.cam = cam_center; A.shininess = shininess;
+        hipLaunchKernelGGL(phong_light_partial_kernel, dim3((unsigned)blocks, (unsigned)N, (unsigned)slots), dim3(RB_BLOCK), 0,
+                           as_stream(stream), A, pl.sweeps, partials);
+        const int rc = check_launch("dss_phong_backward_lights");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(sum_light_partials_kernel, dim3((unsigned)N * (unsigned)slots), dim3(RB_BLOCK), 0, as_stream(stream),
+                       partials, blocks, L, grad_ambient, grad_diffuse, grad_specular, grad_light_vec);
+    return check_launch("dss_phong_backward_lights");
 }

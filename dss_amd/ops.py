@@ -1163,6 +1163,33 @@ def phong_backward_camera(grad_out, world, normals, rgb, cloud_to_packed_first_i
     return gcam
 
 
+def phong_backward_lights(grad_out, world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, ambient,
+                          diffuse_color, specular_color, light_vec, point_lights: bool, cam_center, shininess: float = 64.0,
+                          shared_cloud: bool = False, needs=(True, True, True, True)):
+    """-> (grad_ambient (N,3), grad_diffuse, grad_specular, grad_light_vec (N,L,3)): the shading's gradient w.r.t. the
+    lights (``dss_phong_backward_lights``; same inputs as `phong_backward`), bitwise reproducible.  ``ambient`` is the
+    (N,3) sum over lights, and so is its gradient.  ``needs``: the outputs to compute; the others are returned as None."""
+    lib = _lib.load()
+    world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L = _phong_common(
+        world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
+        specular_color, light_vec, cam_center)
+    grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
+    if tuple(grad_out.shape) != (P, 3):
+        raise RuntimeError("phong_backward_lights: grad_out must be (P,3)")
+    dev = world.device
+    with torch.cuda.device(dev):
+        outs = [torch.empty(shape, dtype=_f32, device=dev) if need else None
+                for need, shape in zip(needs, ((N, 3), (N, L, 3), (N, L, 3), (N, L, 3)))]
+        ws = _lib.workspace(dev, lib.dss_phong_backward_lights_workspace(N, P, L))
+        rc = lib.dss_phong_backward_lights(_lib.ptr(grad_out), _lib.ptr(world), _lib.ptr(normals), _lib.ptr(rgb),
+                                           _lib.ptr(first), _lib.ptr(num), N, Pw, int(shared_cloud), _lib.ptr(amb),
+                                           _lib.ptr(kd), _lib.ptr(ks), _lib.ptr(lv), L, int(point_lights), _lib.ptr(cam),
+                                           float(shininess), *[_lib.ptr(o) for o in outs], _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr(dev))
+    _lib.check(rc, "dss_phong_backward_lights")
+    return tuple(outs)
+
+
 def _mask_u8(mask, name, P, dev):
     if mask is None:
         return None

@@ -5,6 +5,11 @@
 returns a point cloud whose features are ``rgb * (ambient + diffuse) + specular``; one fused HIP kernel each way
 (``dss_phong_forward`` / ``dss_phong_backward``).  This is the path by which an RGB loss reaches the normals (and,
 through point lights and the view direction, the positions).
+
+The lights are differentiable as in the reference, where they are ordinary tensors of the graph: build ``PointLights`` /
+``DirectionalLights`` from tensors that require grad and an RGB loss fills their ``.grad`` (``dss_phong_backward_lights``;
+the sum over lights of the ambient colour and the broadcast of a batch of 1 to the cameras are plain torch views, so
+autograd reduces over them).  Lights that do not require grad cost nothing: the extra reduction is not launched.
 """
 import torch
 import torch.autograd as autograd
@@ -102,7 +107,11 @@ class _Phong(autograd.Function):
         if ctx.needs_input_grad[9]:   # differentiable cameras: the view direction's way back to the camera centre
             gcam = ops.phong_backward_camera(g, world, normals, rgb, first, num, amb, kd, ks, vec, point_lights, cam,
                                              shininess, shared)
-        return (gw, gn, gc) + (None,) * 6 + (gcam,) + (None,) * 3
+        glights = (None,) * 4
+        if any(ctx.needs_input_grad[5:9]):   # learnable lights (amb, kd, ks, vec): reduced over the points of each camera
+            glights = ops.phong_backward_lights(g, world, normals, rgb, first, num, amb, kd, ks, vec, point_lights, cam,
+                                                shininess, shared, needs=ctx.needs_input_grad[5:9])
+        return (gw, gn, gc, None, None) + tuple(glights) + (gcam,) + (None,) * 3
 
 
 class LightingTexture(torch.nn.Module):

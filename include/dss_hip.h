@@ -572,6 +572,30 @@ DSS_API int dss_phong_backward_camera(const float *grad_out, const float *world,
                                       const float *light_vec, int L, int point_lights, const float *cam_center,
                                       float shininess, float *grad_cam /* (N,3) */, void *workspace,
                                       size_t workspace_bytes, void *stream);
+/* Backward of the shading w.r.t. the LIGHTS.  In the reference the lights are ordinary tensors of the autograd graph:
+ * apply_lighting (DSS/core/texture.py:25-63) calls lights.diffuse / lights.specular (DSS/core/lighting.py:10-77, :80-172)
+ * on the tensor properties of PointLights / DirectionalLights (:175-302), and points_rgb * (ambient + diffuse) + specular
+ * (texture.py:118-122) stays on the tape, so light tensors with requires_grad receive gradients from an RGB loss.  With
+ * g = grad_out and c = rgb of a pair, D_l = relu(n^.d^_l), S_l = the specular power of light l, gdv_l = d loss / d d^_l and
+ * u_l = location - x (point lights) or direction (directional lights), summed over the points p of camera n:
+ *   grad_ambient[n] = sum_p g c            grad_diffuse[n][l]   = sum_p g c D_l
+ *   grad_specular[n][l] = sum_p g S_l      grad_light_vec[n][l] = sum_p d(u / max(|u|, 1e-6))^T gdv_l
+ * in the fp32 arithmetic of dss_phong_backward, pair by pair.  Same inputs as dss_phong_backward.  Any of the four outputs
+ * may be NULL; every other one is fully written on every call (Pw == 0, L == 0 and cameras without points: exact zeros).
+ * grad_ambient is the gradient of the (N,3) ambient ALREADY summed over lights.  Bitwise reproducible and independent of
+ * the device, by the two-launch reduction of dss_camera_backward with one 16-float partial per workgroup and
+ * (camera, light): dss_phong_backward_lights_workspace(N, P, L) bytes, P = number of packed pairs; a NULL or short
+ * workspace is DSS_ERR_INVALID_ARGUMENT.  N, L <= 65535. */
+DSS_API size_t dss_phong_backward_lights_workspace(int N, int64_t P, int L);
+DSS_API int dss_phong_backward_lights(const float *grad_out, const float *world, const float *normals,
+                                      const float *rgb, const int64_t *first_idx, const int64_t *num_pts, int N,
+                                      int64_t Pw, int shared_cloud, const float *ambient,
+                                      const float *diffuse_color, const float *specular_color,
+                                      const float *light_vec, int L, int point_lights, const float *cam_center,
+                                      float shininess, float *grad_ambient /* (N,3) */,
+                                      float *grad_diffuse /* (N,L,3) */, float *grad_specular /* (N,L,3) */,
+                                      float *grad_light_vec /* (N,L,3) */, void *workspace,
+                                      size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Point-cloud regularisers of the training iteration (the "both regularisers" of SURVEY 8f rank 2): ProjectionLoss
