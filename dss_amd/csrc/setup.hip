@@ -14,6 +14,8 @@
 // Culled points are not compacted away (that would need a host round trip for the new sizes):
 // they stay in the packed arrays with valid=0 and z=-1, which every downstream kernel ignores
 // (forward: pz<0, rasterize_points.cu:79-80; backward: never visible).
+#include <float.h>
+
 #include "setup_body.h"
 
 namespace dss {
@@ -115,6 +117,8 @@ __global__ __launch_bounds__(256) void project_backward_kernel(
 // PCA frames of the K-neighbourhoods -> anisotropic source variance (rasterizer.py:256-291, mathHelper.py:34-92):
 // covariance of the K nearest points about their mean, cyclic Jacobi in fp32 on the trace-normalised matrix,
 // Vrk = C - c0 e0 e0^T (= the two largest principal components), frame normal e0, curvatures ascending.
+// A cloud of fewer than K points uses the first num_pts[n] list entries (the rest is padding) and divides by that count.
+// A slot that no cloud owns, and a neighbourhood whose trace is zero or below FLT_MIN, get Vrk = 0, e0 = (0,0,1), curvature 0.
 __global__ __launch_bounds__(256) void local_frames_kernel(const float *__restrict__ pts, const int64_t *__restrict__ knn_idx,
                                                            const int64_t *__restrict__ first_idx,
                                                            const int64_t *__restrict__ num_pts, int N, int64_t P, int K,
@@ -147,7 +151,14 @@ __global__ __launch_bounds__(256) void local_frames_kernel(const float *__restri
                 for (int b = 0; b < 3; ++b) C[a][b] += d[a] * d[b] * ik;
         }
         const float tr = C[0][0] + C[1][1] + C[2][2];
-        if (tr > 0.0f) {
+        // a trace below the normal range counts as zero: 1 / tr is not finite there (a NaN trace stays what it was)
+        if (tr > 0.0f && tr < FLT_MIN) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) C[a][b] = 0.f;
+        }
+        if (tr >= FLT_MIN) {
             const float it = 1.0f / tr;
             float A[3][3], V[3][3];
 #pragma unroll
@@ -190,7 +201,8 @@ __global__ __launch_bounds__(256) void local_frames_kernel(const float *__restri
             const bool m0 = l0 <= l1 && l0 <= l2, m1 = !m0 && l1 <= l2;
             const float lmin = m0 ? l0 : (m1 ? l1 : l2);
             const float lmax = fmaxf(l0, fmaxf(l1, l2));
-            const float lmid = (l0 + l1 + l2) - lmin - lmax;
+            // (the difference can round to just outside [lmin, lmax] when two eigenvalues are equal or zero)
+            const float lmid = fminf(fmaxf((l0 + l1 + l2) - lmin - lmax, lmin), lmax);
 #pragma unroll
             for (int k = 0; k < 3; ++k) e0[k] = m0 ? V[k][0] : (m1 ? V[k][1] : V[k][2]);
             lam[0] = lmin * tr; lam[1] = lmid * tr; lam[2] = lmax * tr;

@@ -430,7 +430,13 @@ DSS_API int dss_point_setup(const float *world, const float *normals, const floa
  * cloud-local ids of dss_knn_points (self included); covariance of the K points about their mean, eigen-
  * decomposition (the reference: batched SVD of the centred (K,3) matrix, curvature = sigma^2 / K).  Outputs:
  * vr6 (P,6) = F diag(c1,c2) F^T with F the two principal tangent directions (= C - c0 e0 e0^T), frame_normals
- * (P,3) = e0, curvature (P,3) ascending (may be NULL). */
+ * (P,3) = e0, curvature (P,3) ascending (may be NULL).  Every packed slot of the three outputs is written:
+ *   - a cloud of num_pts[n] < K points: the first num_pts[n] entries of a list count (dss_knn_points pads the rest
+ *     with zeros), and the mean and the covariance divide by num_pts[n];
+ *   - a slot that no cloud owns (outside every [first_idx[n], first_idx[n] + num_pts[n])): vr6 = 0,
+ *     frame_normals = (0,0,1), curvature = 0; its position and its list are not read;
+ *   - a neighbourhood whose covariance has a trace of zero (coincident neighbours, a cloud of one point) or below
+ *     FLT_MIN (1 / trace is not finite): the same constants. */
 DSS_API int dss_local_frames(const float *points /* (P,3) */, const int64_t *knn_idx /* (P,K) */,
                              const int64_t *first_idx, const int64_t *num_pts, int N, int64_t P, int K,
                              float *vr6, float *frame_normals, float *curvature, void *stream);
