@@ -1,7 +1,7 @@
 """ctypes binding of libdss_hip.so (the C ABI declared in include/dss_hip.h).
 
 This module is plumbing only: it turns torch tensors into raw device pointers + sizes, passes
-torch's current HIP stream, and raises ``RuntimeError`` with ``dss_last_error()`` when an entry
+torch's current HIP stream (`call`), and raises ``RuntimeError`` with ``dss_last_error()`` when an entry
 point returns a negative status (the reference raises RuntimeError from TORCH_CHECK / AT_ERROR,
 DSS/csrc/rasterize_points.h:474-488).  There is deliberately NO CPU or pure-torch fallback: if
 the shared library is missing or a tensor is not on a GPU the call fails loudly.
@@ -173,9 +173,34 @@ def require_gpu(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
     return t.contiguous()
 
 
+class _NoSwitch:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
+
+
+_NO_SWITCH = _NoSwitch()
+
+
+def on_device(dev):
+    """`torch.cuda.device(dev)` only when `dev` is not already the current device (the context manager costs ~5 us).
+    Output allocation, the workspace lookup and the call itself belong inside it."""
+    return _NO_SWITCH if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+def call(name: str, dev, *args) -> None:
+    """The one way into an entry point of SIGNATURES that launches: `args` in the order of include/dss_hip.h WITHOUT the
+    trailing stream.  A tensor goes in as its device pointer, None as NULL, scalars as they are (the argtypes convert
+    them); the current stream of `dev` is appended; a non-zero status raises under the entry's name."""
+    rc = getattr(load(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                               torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        check(rc, name)
+
+
 _ws_cache = {}
-
-
 _clean_cache = {}
 
 

@@ -6,6 +6,10 @@ argument meaning, plus the fused entry points.
 All inputs must be GPU tensors; outputs are freshly allocated on the input's device
 (rasterize_points.cu:632-637) except ``_backward_zbuf`` which accumulates in place
 (rasterize_points.h:388-392).
+
+Every operator reads top to bottom as check, allocate, call: the input helpers below state each repeated contract once,
+and ``_lib.call`` is the one place where tensors become pointers, the stream is appended and the status is checked --
+so the argument list at each call site is exactly the C prototype's, minus the stream.
 """
 from typing import Optional, Tuple
 
@@ -15,12 +19,53 @@ import torch
 
 from . import _lib
 
-_f32, _i32, _i64, _u8 = torch.float32, torch.int32, torch.int64, torch.uint8
+_f32, _i32, _i64, _u8, _f64 = torch.float32, torch.int32, torch.int64, torch.uint8, torch.float64
+_on_device = _lib.on_device
+
+
+def _gpu(dtype, **tensors):
+    """`_lib.require_gpu` of several tensors of one dtype, in the order given; the keyword is the name in the message."""
+    return [_lib.require_gpu(t, name, dtype) for name, t in tensors.items()]
+
+
+def _ranges(cloud_to_packed_first_idx, num_points_per_cloud):
+    """The packed cloud ranges that almost every operator takes -> (first, num, N)."""
+    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
+    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    return first, num, first.shape[0]
 
 
 def _as_u8(mask):
     """bool -> uint8 without a copy kernel (same storage, values 0/1)."""
     return mask.view(_u8) if mask.dtype == torch.bool else mask
+
+
+def _flags(mask, name):
+    """Per-point flags for the kernels: bool or uint8 (any other dtype is refused, unlike `_mask_u8`)."""
+    return _lib.require_gpu(_as_u8(mask), name, _u8)
+
+
+def _h_mode(h, N: int, Pw: int, P: int, shared) -> int:
+    """What the entries of `h` stand for: 0 = one per cloud, 1 = one per world point, 2 = one per PACKED point (a shared
+    cloud whose cameras cull differently: one value per (camera, point) pair).  As many clouds as points reads per cloud."""
+    n = h.numel()
+    if n == Pw and not (n == N and Pw == N):
+        return 1
+    if shared and N > 1 and n == P:
+        return 2
+    if n != N:
+        raise RuntimeError("h must have %d (per point), %d (per cloud) or, for a shared cloud, %d (per packed point) entries" % (Pw, N, P))
+    return 0
+
+
+def _check_cameras(M, V, znear, zfar, N):
+    if tuple(M.shape) != (N, 4, 4) or tuple(V.shape) != (N, 4, 4) or znear.numel() != N or zfar.numel() != N:
+        raise RuntimeError("camera tensors must be M,V (N,4,4) and znear,zfar (N,) with N=%d" % N)
+
+
+def _dense(t, shape, dtype=_f32) -> bool:
+    """whether a caller-owned output buffer is a contiguous `dtype` tensor of `shape` (an int: of that many elements)"""
+    return t.dtype == dtype and t.is_contiguous() and (t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == shape)
 
 
 def _check_raster_inputs(points, ellipse_params, cutoff_thres, radii, first_idx, num_pts):
@@ -39,6 +84,12 @@ def _check_raster_inputs(points, ellipse_params, cutoff_thres, radii, first_idx,
     return P
 
 
+def _fragments(dev, N, rows, S, K):
+    """the four fragment outputs of a splat: idx, zbuf, qvalue (N,rows,S,K) and occupancy (N,rows,S)"""
+    return (torch.empty((N, rows, S, K), dtype=_i32, device=dev), torch.empty((N, rows, S, K), dtype=_f32, device=dev),
+            torch.empty((N, rows, S, K), dtype=_f32, device=dev), torch.empty((N, rows, S), dtype=_f32, device=dev))
+
+
 def splat_points(points, ellipse_params, cutoff_thres, radii, cloud_to_packed_first_idx,
                  num_points_per_cloud, depth_merging_thres: float, image_size: int,
                  points_per_pixel: int, bin_size: Optional[int] = None,
@@ -53,39 +104,26 @@ def splat_points(points, ellipse_params, cutoff_thres, radii, cloud_to_packed_fi
     ``rows=(row0,row1)`` renders only that row band (outputs are band shaped);
     ``return_visible`` appends the per-point visibility mask (bool (P,)).
     """
-    lib = _lib.load()
     P = _check_raster_inputs(points, ellipse_params, cutoff_thres, radii, cloud_to_packed_first_idx,
                              num_points_per_cloud)
-    points = _lib.require_gpu(points, "points", _f32)
+    points, ellipse_params, cutoff_thres, radii = _gpu(_f32, points=points, ellipse_params=ellipse_params,
+                                                       cutoff_thres=cutoff_thres, radii=radii)
     dev = points.device
-    ellipse_params = _lib.require_gpu(ellipse_params, "ellipse_params", _f32)
-    cutoff_thres = _lib.require_gpu(cutoff_thres, "cutoff_thres", _f32)
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N, S, K = first.shape[0], int(image_size), int(points_per_pixel)
-    row0, row1 = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    S, K = int(image_size), int(points_per_pixel)
+    row0, row1, _ = _band(rows, S)
     nrows = max(row1 - row0, 0)
     bs = 1 if bin_size is None else int(bin_size)
-    with torch.cuda.device(dev):
-        idx = torch.empty((N, nrows, S, K), dtype=_i32, device=dev)
-        zbuf = torch.empty((N, nrows, S, K), dtype=_f32, device=dev)
-        qv = torch.empty((N, nrows, S, K), dtype=_f32, device=dev)
-        occ = torch.empty((N, nrows, S), dtype=_f32, device=dev)
+    with _on_device(dev):
+        idx, zbuf, qv, occ = _fragments(dev, N, nrows, S, K)
         vis = torch.empty((P,), dtype=_u8, device=dev) if return_visible else None
         if nrows == 0:  # a rank whose row band is empty (RowPartition with S < world_size * band): nothing to launch
             if vis is not None:
                 vis.zero_()
-                return idx, zbuf, qv, occ, vis.view(torch.bool)
-            return idx, zbuf, qv, occ
-        nbytes = lib.dss_splat_forward_workspace(N, P, S, K, bs)
-        ws = _lib.workspace(dev, nbytes)
-        rc = lib.dss_splat_forward(_lib.ptr(points), _lib.ptr(ellipse_params), _lib.ptr(cutoff_thres),
-                                   _lib.ptr(radii), _lib.ptr(first), _lib.ptr(num), N, P,
-                                   float(depth_merging_thres), S, K, bs, row0, row1,
-                                   _lib.ptr(idx), _lib.ptr(zbuf), _lib.ptr(qv), _lib.ptr(occ), _lib.ptr(vis),
-                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_splat_forward")
+        else:
+            ws = _lib.workspace(dev, _lib.load().dss_splat_forward_workspace(N, P, S, K, bs))
+            _lib.call("dss_splat_forward", dev, points, ellipse_params, cutoff_thres, radii, first, num, N, P,
+                      float(depth_merging_thres), S, K, bs, row0, row1, idx, zbuf, qv, occ, vis, ws, ws.numel())
     if return_visible:
         return idx, zbuf, qv, occ, vis.view(torch.bool)  # zero-copy reinterpretation (values are 0/1)
     return idx, zbuf, qv, occ
@@ -98,41 +136,10 @@ def _splat_points_naive(points, ellipse_params, cutoff_thres, radii, cloud_to_pa
                         num_points_per_cloud, depth_merging_thres, image_size, points_per_pixel, 0, 0)
 
 
-def _rasterize_coarse(points, radii, cloud_to_packed_first_idx, num_points_per_cloud, image_size: int, bin_size: int,
-                      max_points_per_bin: int):
-    """``DSS._C._rasterize_coarse`` (ext.cpp:11, rasterize_points.h:167-203): the binning pass alone.  The reference
-    returns a dense ``(N, B, B, M)`` int32 table; here ``bin_points`` is an OPAQUE uint8 tensor (the tile-list workspace
-    of ``dss_splat_bin``: per-tile sub-list counters + fixed-capacity id lists over 8x8-pixel tiles) that is only meant
-    to be handed to :func:`_rasterize_fine`.  ``bin_size`` / ``max_points_per_bin`` are accepted and ignored (tile size
-    and list capacity are chosen by the library; lists never truncate)."""
-    lib = _lib.load()
-    src = _bin_source(points, radii)   # what the CALLER handed over (before any normalisation copy)
-    points = _lib.require_gpu(points, "points", _f32)
-    dev = points.device
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    if points.dim() != 2 or points.shape[1] != 3 or tuple(radii.shape) != (points.shape[0], 2):
-        raise RuntimeError("points must be (P,3) and radii (P,2)")
-    N, P, S = first.shape[0], points.shape[0], int(image_size)
-    with torch.cuda.device(dev):
-        nbytes = lib.dss_splat_forward_workspace(N, P, S, 1, 1)
-        bin_points = torch.empty(nbytes, dtype=_u8, device=dev)
-        if P > 0:
-            rc = lib.dss_splat_bin(_lib.ptr(points), _lib.ptr(radii), _lib.ptr(first), _lib.ptr(num), N, P, S, 0, S,
-                                   _lib.ptr(bin_points), nbytes, _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_splat_bin")
-    # what the fine pass needs besides the lists, and what the lists were built from.  Kept in a registry keyed by the
-    # buffer's address (not as a Python attribute of the tensor, which views, autograd saves and `detach()` drop): any
-    # tensor that still refers to this storage finds it; a copy (clone / to) does not and is refused with a clear message.
-    # keyed by the STORAGE address, so that a view with a storage offset still finds its entry
-    _bin_registry[bin_points.untyped_storage().data_ptr()] = (weakref.ref(bin_points), first, num, N, P, S, src)
-    if len(_bin_registry) > 64:
-        for k in [k for k, v in _bin_registry.items() if v[0]() is None]:
-            del _bin_registry[k]
-    return bin_points
-
-
+# What the fine pass needs besides the tile lists of `_rasterize_coarse`, and what the lists were built from.  Kept in a
+# registry keyed by the buffer's address (not as a Python attribute of the tensor, which views, autograd saves and
+# `detach()` drop): any tensor that still refers to this storage finds it; a copy (clone / to) does not and is refused with
+# a clear message.  Keyed by the STORAGE address, so that a view with a storage offset still finds its entry.
 _bin_registry = {}
 
 
@@ -143,11 +150,36 @@ def _bin_source(points, radii):
     return tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version) for t in (points, radii))
 
 
+def _rasterize_coarse(points, radii, cloud_to_packed_first_idx, num_points_per_cloud, image_size: int, bin_size: int,
+                      max_points_per_bin: int):
+    """``DSS._C._rasterize_coarse`` (ext.cpp:11, rasterize_points.h:167-203): the binning pass alone.  The reference
+    returns a dense ``(N, B, B, M)`` int32 table; here ``bin_points`` is an OPAQUE uint8 tensor (the tile-list workspace
+    of ``dss_splat_bin``: per-tile sub-list counters + fixed-capacity id lists over 8x8-pixel tiles) that is only meant
+    to be handed to :func:`_rasterize_fine`.  ``bin_size`` / ``max_points_per_bin`` are accepted and ignored (tile size
+    and list capacity are chosen by the library; lists never truncate)."""
+    src = _bin_source(points, radii)   # what the CALLER handed over (before any normalisation copy)
+    points, radii = _gpu(_f32, points=points, radii=radii)
+    dev = points.device
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    if points.dim() != 2 or points.shape[1] != 3 or tuple(radii.shape) != (points.shape[0], 2):
+        raise RuntimeError("points must be (P,3) and radii (P,2)")
+    P, S = points.shape[0], int(image_size)
+    with _on_device(dev):
+        nbytes = _lib.load().dss_splat_forward_workspace(N, P, S, 1, 1)
+        bin_points = torch.empty(nbytes, dtype=_u8, device=dev)
+        if P > 0:
+            _lib.call("dss_splat_bin", dev, points, radii, first, num, N, P, S, 0, S, bin_points, nbytes)
+    _bin_registry[bin_points.untyped_storage().data_ptr()] = (weakref.ref(bin_points), first, num, N, P, S, src)
+    if len(_bin_registry) > 64:
+        for k in [k for k, v in _bin_registry.items() if v[0]() is None]:
+            del _bin_registry[k]
+    return bin_points
+
+
 def _rasterize_fine(points, ellipse_params, cutoff_thres, radii, bin_points, depth_merging_thres: float, image_size: int,
                     bin_size: int, points_per_pixel: int):
     """``DSS._C._rasterize_fine`` (ext.cpp:12, rasterize_points.h:257-285) on the ``bin_points`` of
     :func:`_rasterize_coarse` -> ``(idx, zbuf, qvalue, occupancy)`` like ``splat_points``."""
-    lib = _lib.load()
     meta = _bin_registry.get(bin_points.untyped_storage().data_ptr()) \
         if isinstance(bin_points, torch.Tensor) and bin_points.is_cuda else None
     if meta is None or meta[0]() is None:
@@ -160,22 +192,13 @@ def _rasterize_fine(points, ellipse_params, cutoff_thres, radii, bin_points, dep
     if src != _bin_source(points, radii):
         raise RuntimeError("bin_points were built from other points / radii tensors (or these were modified since)")
     _check_raster_inputs(points, ellipse_params, cutoff_thres, radii, first, num)
-    points = _lib.require_gpu(points, "points", _f32)
-    dev = points.device
-    ellipse_params = _lib.require_gpu(ellipse_params, "ellipse_params", _f32)
-    cutoff_thres = _lib.require_gpu(cutoff_thres, "cutoff_thres", _f32)
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    K = int(points_per_pixel)
-    with torch.cuda.device(dev):
-        idx = torch.empty((N, S, S, K), dtype=_i32, device=dev)
-        zbuf = torch.empty((N, S, S, K), dtype=_f32, device=dev)
-        qv = torch.empty((N, S, S, K), dtype=_f32, device=dev)
-        occ = torch.empty((N, S, S), dtype=_f32, device=dev)
-        rc = lib.dss_splat_fine(_lib.ptr(points), _lib.ptr(ellipse_params), _lib.ptr(cutoff_thres), _lib.ptr(radii),
-                                _lib.ptr(first), _lib.ptr(num), N, P, float(depth_merging_thres), S, K, 0, S, _lib.ptr(idx),
-                                _lib.ptr(zbuf), _lib.ptr(qv), _lib.ptr(occ), None, _lib.ptr(whole) if P > 0 else None,
-                                whole.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_splat_fine")
+    points, ellipse_params, cutoff_thres, radii = _gpu(_f32, points=points, ellipse_params=ellipse_params,
+                                                       cutoff_thres=cutoff_thres, radii=radii)
+    dev, K = points.device, int(points_per_pixel)
+    with _on_device(dev):
+        idx, zbuf, qv, occ = _fragments(dev, N, S, S, K)
+        _lib.call("dss_splat_fine", dev, points, ellipse_params, cutoff_thres, radii, first, num, N, P,
+                  float(depth_merging_thres), S, K, 0, S, idx, zbuf, qv, occ, None, whole if P > 0 else None, whole.numel())
     return idx, zbuf, qv, occ
 
 
@@ -184,23 +207,18 @@ def _splat_points_occ_backward(points, radii, grad_occ, cloud_to_packed_first_id
     """``DSS._C._splat_points_occ_backward`` on GPU tensors (ext.cpp:10, 16; rasterize_points.cu:672-822): the
     box-supported occupancy surrogate over ALL points handed in -> (P,2).  Not on the training path
     (``backward_occ_fast = True``, rasterizer.py:816).  ``depth_merging_thres`` is unused, as in the reference."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
+    points, radii, grad_occ = _gpu(_f32, points=points, radii=radii, grad_occ=grad_occ)
     dev = points.device
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    grad_occ = _lib.require_gpu(grad_occ, "grad_occ", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     if points.dim() != 2 or points.shape[1] != 3 or tuple(radii.shape) != (points.shape[0], 2) or first.shape != num.shape:
         raise RuntimeError("points must be (P,3), radii (P,2), first_idx / num_points (N,)")  # rasterize_points.h:357-361
-    N, P = first.shape[0], points.shape[0]
+    P = points.shape[0]
     if grad_occ.dim() != 3 or grad_occ.shape[0] != N or grad_occ.shape[1] != grad_occ.shape[2]:
         raise RuntimeError("grad_occ must be (N,S,S) with N=%d, got %s" % (N, tuple(grad_occ.shape)))
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         grad = torch.empty((P, 2), dtype=_f32, device=dev)
-        rc = lib.dss_occ_backward_box(_lib.ptr(points), _lib.ptr(radii), _lib.ptr(grad_occ), _lib.ptr(first), _lib.ptr(num),
-                                      N, P, grad_occ.shape[1], float(radii_s), _lib.ptr(grad), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_occ_backward_box")
+        _lib.call("dss_occ_backward_box", dev, points, radii, grad_occ, first, num, N, P, grad_occ.shape[1],
+                  float(radii_s), grad)
     return grad
 
 
@@ -218,19 +236,15 @@ def _splat_points_occ_fast_cuda_backward(points_sorted, radii_sorted, rs, grad_o
 
 def backward_radius(radii, visible, cloud_to_packed_first_idx, num_points_per_cloud, radii_s: float):
     """Search radius of the backward pass, rasterizer.py:885-888 -> f32 (N,)."""
-    lib = _lib.load()
     radii = _lib.require_gpu(radii, "radii", _f32)
     dev = radii.device
-    vis = _lib.require_gpu(_as_u8(visible), "visible", _u8)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N, P = first.shape[0], radii.shape[0]
-    with torch.cuda.device(dev):
+    vis = _flags(visible, "visible")
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    P = radii.shape[0]
+    with _on_device(dev):
         rs = torch.empty((N,), dtype=_f32, device=dev)
-        ws = _lib.workspace(dev, lib.dss_backward_radius_workspace(N, P))
-        rc = lib.dss_backward_radius(_lib.ptr(radii), _lib.ptr(vis), _lib.ptr(first), _lib.ptr(num), N, P,
-                                     float(radii_s), _lib.ptr(rs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_backward_radius")
+        ws = _lib.workspace(dev, _lib.load().dss_backward_radius_workspace(N, P))
+        _lib.call("dss_backward_radius", dev, radii, vis, first, num, N, P, float(radii_s), rs, ws, ws.numel())
     return rs
 
 
@@ -250,35 +264,29 @@ def occ_backward(points, radii, visible, rs, grad_occ, cloud_to_packed_first_idx
     (rasterizer.py:889-950) + ``DSS._C._splat_points_occ_fast_cuda_backward`` (ext.cpp:14).
     ``grad_occ`` may be a strided channel view of an image gradient (read in place).  ``clip > 0`` fuses
     the per-point clip hook (valid only when no zbuf gradient / cross-rank reduction follows)."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
+    points, radii = _gpu(_f32, points=points, radii=radii)
     dev = points.device
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    vis = _lib.require_gpu(_as_u8(visible), "visible", _u8)
+    vis = _flags(visible, "visible")
     rs = _lib.require_gpu(rs, "rs", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N, P = first.shape[0], points.shape[0]
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    P = points.shape[0]
     S = int(image_size) if image_size is not None else grad_occ.shape[2]
-    row0, row1 = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
+    row0, row1, _ = _band(rows, S)
     if tuple(grad_occ.shape) != (N, row1 - row0, S):
         raise RuntimeError("grad_occ must have shape (%d, %d, %d), got %s" % (N, row1 - row0, S, tuple(grad_occ.shape)))
     if row1 <= row0:  # empty band: no pixel contributes
         return torch.zeros((P, 3), dtype=_f32, device=dev)
     grad_occ, gstride = _pixel_strided(grad_occ, N, row1 - row0, S)
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         grad = torch.empty((P, 3), dtype=_f32, device=dev)
-        rc = lib.dss_occ_backward(_lib.ptr(points), _lib.ptr(radii), _lib.ptr(vis), _lib.ptr(rs), _lib.ptr(grad_occ),
-                                  _lib.ptr(first), _lib.ptr(num), N, P, S, row0, row1, gstride, float(clip),
-                                  _lib.ptr(grad), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_occ_backward")
+        _lib.call("dss_occ_backward", dev, points, radii, vis, rs, grad_occ, first, num, N, P, S, row0, row1, gstride,
+                  float(clip), grad)
     return grad
 
 
 def _backward_zbuf(idx, grad_zbuf, point_grad):
     """``DSS._C._backward_zbuf`` (ext.cpp:17): in-place scatter-add.  ``point_grad`` is either the
     reference's (P,1) z-gradient tensor or a (P,3) point-gradient tensor (z column updated)."""
-    lib = _lib.load()
     idx = _lib.require_gpu(idx, "idx", _i32)
     dev = idx.device
     grad_zbuf = _lib.require_gpu(grad_zbuf, "grad_zbuf", _f32)
@@ -286,40 +294,33 @@ def _backward_zbuf(idx, grad_zbuf, point_grad):
         raise RuntimeError("idx and grad_zbuf must both be (N,H,W,K)")
     if not (point_grad.is_cuda and point_grad.dtype == _f32 and point_grad.is_contiguous() and point_grad.dim() == 2):
         raise RuntimeError("point_grad must be a contiguous float32 GPU tensor of shape (P,1) or (P,3)")
+    if point_grad.shape[1] not in (1, 3):
+        raise RuntimeError("point_grad must have 1 or 3 columns")
     N, H, W, K = idx.shape
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         if point_grad.shape[1] == 3:
-            rc = lib.dss_zbuf_backward(_lib.ptr(idx), _lib.ptr(grad_zbuf), N, H, W, K, _lib.ptr(point_grad),
-                                       _lib.stream_ptr(dev))
-        elif point_grad.shape[1] == 1:
-            tmp = torch.zeros((point_grad.shape[0], 3), dtype=_f32, device=dev)
-            rc = lib.dss_zbuf_backward(_lib.ptr(idx), _lib.ptr(grad_zbuf), N, H, W, K, _lib.ptr(tmp),
-                                       _lib.stream_ptr(dev))
-            point_grad += tmp[:, 2:3]
+            _lib.call("dss_zbuf_backward", dev, idx, grad_zbuf, N, H, W, K, point_grad)
         else:
-            raise RuntimeError("point_grad must have 1 or 3 columns")
-    _lib.check(rc, "dss_zbuf_backward")
+            tmp = torch.zeros((point_grad.shape[0], 3), dtype=_f32, device=dev)
+            _lib.call("dss_zbuf_backward", dev, idx, grad_zbuf, N, H, W, K, tmp)
+            point_grad += tmp[:, 2:3]
 
 
 def clip_grad_(grad_pts, clip: float):
     """In-place per-point norm clip (rasterizer.py:667-673)."""
-    lib = _lib.load()
     if not (grad_pts.is_cuda and grad_pts.dtype == _f32 and grad_pts.is_contiguous()):
         raise RuntimeError("grad_pts must be a contiguous float32 GPU tensor")
-    with torch.cuda.device(grad_pts.device):
-        rc = lib.dss_clip_grad(_lib.ptr(grad_pts), grad_pts.shape[0], float(clip), _lib.stream_ptr(grad_pts.device))
-    _lib.check(rc, "dss_clip_grad")
+    with _on_device(grad_pts.device):
+        _lib.call("dss_clip_grad", grad_pts.device, grad_pts, grad_pts.shape[0], float(clip))
     return grad_pts
 
 
 def splat_backward(points, radii, visible, idx, grad_occ, grad_zbuf, cloud_to_packed_first_idx,
                    num_points_per_cloud, radii_s: float, clip: float = -1.0, return_rs: bool = False):
     """Whole ``EllipticalRasterizer.backward`` (rasterizer.py:787-977) in one call -> grad (P,3)."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
+    points, radii = _gpu(_f32, points=points, radii=radii)
     dev = points.device
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    vis = _lib.require_gpu(_as_u8(visible), "visible", _u8)
+    vis = _flags(visible, "visible")
     idx = _lib.require_gpu(idx, "idx", _i32)
     if grad_occ is None:  # (autograd hands over None for an unused output: only then are zeros allocated)
         grad_occ = torch.zeros(idx.shape[:3], dtype=_f32, device=dev)
@@ -327,42 +328,31 @@ def splat_backward(points, radii, visible, idx, grad_occ, grad_zbuf, cloud_to_pa
         raise RuntimeError("dss_amd: grad_occ must be a GPU tensor (no CPU fallback)")
     if grad_zbuf is not None:
         grad_zbuf = _lib.require_gpu(grad_zbuf, "grad_zbuf", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, _ = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     N, S, _, K = idx.shape
     P = points.shape[0]
     grad_occ, gstride = _pixel_strided(grad_occ, N, S, S)
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         grad = torch.empty((P, 3), dtype=_f32, device=dev)
         rs = torch.empty((N,), dtype=_f32, device=dev)
-        ws = _lib.workspace(dev, lib.dss_splat_backward_workspace(N, P))
-        rc = lib.dss_splat_backward(_lib.ptr(points), _lib.ptr(radii), _lib.ptr(vis), _lib.ptr(idx),
-                                    _lib.ptr(grad_occ), _lib.ptr(grad_zbuf), _lib.ptr(first), _lib.ptr(num),
-                                    N, P, S, K, gstride, float(radii_s), float(clip), _lib.ptr(grad), _lib.ptr(rs),
-                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_splat_backward")
+        ws = _lib.workspace(dev, _lib.load().dss_splat_backward_workspace(N, P))
+        _lib.call("dss_splat_backward", dev, points, radii, vis, idx, grad_occ, grad_zbuf, first, num, N, P, S, K, gstride,
+                  float(radii_s), float(clip), grad, rs, ws, ws.numel())
     return (grad, rs) if return_rs else grad
 
 
 def blend_forward(idx, qvalue, occupancy, scaler, features, return_wsum: bool = False):
     """Fused weights + NormWeightedCompositor + RGBA assembly (renderer.py:53-78).
     ``features`` is (P,C); returns (N,H,W,C+1) [and the per-pixel weight sum max(sum w, 1e-4)]."""
-    lib = _lib.load()
     idx = _lib.require_gpu(idx, "idx", _i32)
     dev = idx.device
-    qvalue = _lib.require_gpu(qvalue, "qvalue", _f32)
-    occupancy = _lib.require_gpu(occupancy, "occupancy", _f32)
-    scaler = _lib.require_gpu(scaler, "scaler", _f32)
-    features = _lib.require_gpu(features, "features", _f32)
+    qvalue, occupancy, scaler, features = _gpu(_f32, qvalue=qvalue, occupancy=occupancy, scaler=scaler, features=features)
     N, H, W, K = idx.shape
     C = features.shape[1]
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         out = torch.empty((N, H, W, C + 1), dtype=_f32, device=dev)
         wsum = torch.empty((N, H, W), dtype=_f32, device=dev) if return_wsum else None
-        rc = lib.dss_blend_forward(_lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(occupancy), _lib.ptr(scaler),
-                                   _lib.ptr(features), N, H, W, K, C, _lib.ptr(out), _lib.ptr(wsum),
-                                   _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_blend_forward")
+        _lib.call("dss_blend_forward", dev, idx, qvalue, occupancy, scaler, features, N, H, W, K, C, out, wsum)
     return (out, wsum) if return_wsum else out
 
 
@@ -373,38 +363,29 @@ def blend_backward(grad_out, idx, qvalue, scaler, num_points: int, geometry=None
     ``geometry = (pts_screen, radii, visible, first_idx, num_points_per_cloud)`` selects the
     point-centric gather kernel (no atomics, deterministic); without it the pixel-centric scatter
     kernel is used."""
-    lib = _lib.load()
     grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
     dev = grad_out.device
     idx = _lib.require_gpu(idx, "idx", _i32)
-    qvalue = _lib.require_gpu(qvalue, "qvalue", _f32)
-    scaler = _lib.require_gpu(scaler, "scaler", _f32)
+    qvalue, scaler = _gpu(_f32, qvalue=qvalue, scaler=scaler)
     N, H, W, K = idx.shape
     C = grad_out.shape[-1] - 1
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         gf = torch.empty((num_points, C), dtype=_f32, device=dev)
         if geometry is None:
-            rc = lib.dss_blend_backward_scatter(_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(scaler),
-                                                N, H, W, K, C, num_points, _lib.ptr(gf), _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_blend_backward_scatter")
+            _lib.call("dss_blend_backward_scatter", dev, grad_out, idx, qvalue, scaler, N, H, W, K, C, num_points, gf)
         else:
             pts, radii, vis, first, num = geometry
-            pts = _lib.require_gpu(pts, "pts_screen", _f32)
-            radii = _lib.require_gpu(radii, "radii", _f32)
-            vis = _lib.require_gpu(_as_u8(vis), "visible", _u8)
-            first = _lib.require_gpu(first, "cloud_to_packed_first_idx", _i64)
-            num = _lib.require_gpu(num, "num_points_per_cloud", _i64)
+            pts, radii = _gpu(_f32, pts_screen=pts, radii=radii)
+            vis = _flags(vis, "visible")
+            first, num, n_clouds = _ranges(first, num)
             if wsum is not None:
                 wsum = _lib.require_gpu(wsum, "wsum", _f32)
             S = int(image_size) if image_size is not None else W
-            row0, row1 = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
+            row0, row1, _ = _band(rows, S)
             if H != row1 - row0 or W != S:
                 raise RuntimeError("fragment tensors must be (N, %d, %d, K)" % (row1 - row0, S))
-            rc = lib.dss_blend_backward(_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(wsum),
-                                        _lib.ptr(scaler), _lib.ptr(pts), _lib.ptr(radii), _lib.ptr(vis),
-                                        _lib.ptr(first), _lib.ptr(num), first.shape[0], num_points, S, K, C, row0,
-                                        row1, _lib.ptr(gf), _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_blend_backward")
+            _lib.call("dss_blend_backward", dev, grad_out, idx, qvalue, wsum, scaler, pts, radii, vis, first, num,
+                      n_clouds, num_points, S, K, C, row0, row1, gf)
     return gf, grad_out[..., C]
 
 
@@ -480,30 +461,18 @@ def render_forward(world, normals, h, M, V, znear, zfar, cloud_to_packed_first_i
     written for the splats that meet the band only (zero elsewhere); everything else is unchanged -- what a multi-GPU
     rank asks for: it needs every point's position and radii for the backward, but bins an eighth of the cloud.
     ``point_outputs`` = (ellipse (P,3), scaler (P,), cutoff (P,)): caller-owned buffers for those three outputs."""
-    lib = _lib.load()
-    world = _lib.require_gpu(world, "world", _f32)
+    world, normals, h, M, V, znear, zfar = _gpu(_f32, world=world, normals=normals, h=h, M=M, V=V, znear=znear, zfar=zfar)
     dev = world.device
-    normals = _lib.require_gpu(normals, "normals", _f32)
-    h = _lib.require_gpu(h, "h", _f32)
-    M = _lib.require_gpu(M, "M", _f32)
-    V = _lib.require_gpu(V, "V", _f32)
-    znear = _lib.require_gpu(znear, "znear", _f32)
-    zfar = _lib.require_gpu(zfar, "zfar", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     features = _lib.require_gpu(features, "features", _f32)
-    N, Pw = first.shape[0], world.shape[0]
-    if tuple(M.shape) != (N, 4, 4) or tuple(V.shape) != (N, 4, 4) or znear.numel() != N or zfar.numel() != N:
-        raise RuntimeError("camera tensors must be M,V (N,4,4) and znear,zfar (N,) with N=%d" % N)
+    Pw = world.shape[0]
+    _check_cameras(M, V, znear, zfar, N)
     if normals.shape != world.shape:
         raise RuntimeError("normals must match world points")
     P = N * Pw if shared_cloud else Pw
     if features.shape[0] != P:
         raise RuntimeError("features must be packed (P,C) with P=%d, got %s" % (P, tuple(features.shape)))
-    per_point = h.numel() == Pw and not (h.numel() == N and Pw == N)
-    packed_h = (not per_point) and shared_cloud and N > 1 and h.numel() == P    # one value per (camera, point) pair
-    if not per_point and not packed_h and h.numel() != N:
-        raise RuntimeError("h must have %d (per point), %d (per cloud) or, for a shared cloud, %d (per packed point) entries" % (Pw, N, P))
+    h_mode = _h_mode(h, N, Pw, P, shared_cloud)
     S, K, C = int(image_size), int(points_per_pixel), features.shape[1]
     row0, row1, cyc = _band(rows, S)
     nr = band_rows(row0, row1, cyc)
@@ -516,17 +485,17 @@ def render_forward(world, normals, h, M, V, znear, zfar, cloud_to_packed_first_i
         o.update(idx=e(N, 0, S, K, dtype=_i32), zbuf=e(N, 0, S, K), qvalue=e(N, 0, S, K), occupancy=e(N, 0, S),
                  image=e(N, 0, S, C + 1) if out_image is None else out_image, wsum=e(N, 0, S), visible=vis.view(torch.bool))
         return o
-    with torch.cuda.device(dev):
+    ws_mode = int(workspace_state) & 0xf
+    with _on_device(dev):
         # band_outputs_only: the library writes ellipse / scaler / cutoff only for the splats that meet the band; the rest of
         # those three arrays is handed out ZERO-filled, never as uninitialised device memory (one fill of 20 P bytes)
         if point_outputs is not None:
             # caller-owned (ellipse (P,3), scaler (P,), cutoff (P,)): a multi-GPU step zero-fills them ONCE and hands them to
             # every forward (entries of splats outside the band then hold zeros or the value of an earlier step: defined)
             ell, sca, cut = point_outputs
-            if tuple(ell.shape) != (P, 3) or tuple(sca.shape) != (P,) or tuple(cut.shape) != (P,) or \
-                    any(t.dtype != _f32 or not t.is_contiguous() or t.device != dev for t in (ell, sca, cut)):
+            if not (_dense(ell, (P, 3)) and _dense(sca, (P,)) and _dense(cut, (P,))) or any(t.device != dev for t in point_outputs):
                 raise RuntimeError("point_outputs must be contiguous float32 (P,3), (P,), (P,) tensors on the device")
-        elif band_outputs_only and (int(workspace_state) & 0xf) != 2:
+        elif band_outputs_only and ws_mode != 2:
             z3 = torch.zeros(P * 5, dtype=_f32, device=dev)
             ell, sca, cut = z3[:P * 3].view(P, 3), z3[P * 3:P * 4], z3[P * 4:]
         else:
@@ -542,25 +511,22 @@ def render_forward(world, normals, h, M, V, znear, zfar, cloud_to_packed_first_i
                 or tuple(vis.shape) != (P,) or vis.dtype != _u8:
             raise RuntimeError("out_image must be float32 (N,rows,S,C+1), 16-byte aligned, with contiguous rows "
                                "(any camera / row strides that are multiples of 4 floats); out_visible uint8 (P,)")
-        _keep, vr_p, fn_p = _aniso_args(vr6, frame_normals, Pw)
+        vr6, frame_normals = _aniso_args(vr6, frame_normals, Pw)
         # dedicated zero-initialised buffer per problem size: the library keeps it clean (no memset launch)
-        tag = ("render_forward" if (int(workspace_state) & 0xf) == 1 else "render_forward_binned", N, P, S)
-        ws = _lib.clean_workspace(dev, tag, lib.dss_render_forward_workspace(N, P, S, K))
+        tag = ("render_forward" if ws_mode == 1 else "render_forward_binned", N, P, S)
+        ws = _lib.clean_workspace(dev, tag, _lib.load().dss_render_forward_workspace(N, P, S, K))
         state = _order_state(ws, int(workspace_state), (N, P, S), order_refresh)
-        if band_outputs_only and (int(workspace_state) & 0xf) != 2:
+        if band_outputs_only and ws_mode != 2:
             state |= _lib.WS_BAND_OUTPUTS
-        rc = lib.dss_render_forward(
-            _lib.ptr(world), _lib.ptr(normals), _lib.ptr(h) if (per_point or packed_h) else None, None if per_point else _lib.ptr(h),
-            vr_p, fn_p, _lib.ptr(M), _lib.ptr(V), _lib.ptr(znear), _lib.ptr(zfar), _lib.ptr(first), _lib.ptr(num), N, P,
-            int(shared_cloud), int(backface_culling), S, K, float(cutoff_threshold), float(antialiasing_sigma),
-            float(depth_merging_thres), row0, row1, cyc, _lib.ptr(features), C, _lib.ptr(o["pts_screen"]),
-            _lib.ptr(o["ellipse_params"]), _lib.ptr(o["radii"]), _lib.ptr(o["scaler"]), _lib.ptr(o["cutoff_threshold"]),
-            _lib.ptr(valid), _lib.ptr(o["idx"]), _lib.ptr(o["zbuf"]), _lib.ptr(o["qvalue"]), _lib.ptr(o["occupancy"]),
-            _lib.ptr(vis), _lib.ptr(img), int(img.stride(0)), int(img.stride(1)), _lib.ptr(o["wsum"]), _lib.ptr(ws),
-            ws.numel(), state, _lib.stream_ptr(dev))
-        if rc:
+        try:
+            _lib.call("dss_render_forward", dev, world, normals, h if h_mode else None, None if h_mode == 1 else h,
+                      vr6, frame_normals, M, V, znear, zfar, first, num, N, P, int(shared_cloud), int(backface_culling), S, K,
+                      float(cutoff_threshold), float(antialiasing_sigma), float(depth_merging_thres), row0, row1, cyc,
+                      features, C, o["pts_screen"], ell, o["radii"], sca, cut, valid, o["idx"], o["zbuf"], o["qvalue"],
+                      o["occupancy"], vis, img, int(img.stride(0)), int(img.stride(1)), o["wsum"], ws, ws.numel(), state)
+        except RuntimeError:
             _lib.drop_clean_workspace(dev, tag)
-    _lib.check(rc, "dss_render_forward")
+            raise
     o["valid"], o["visible"] = valid.view(torch.bool), vis.view(torch.bool)
     return o
 
@@ -584,17 +550,12 @@ def render_backward(grad_out, idx, qvalue, wsum, scaler, points, radii, visible,
     can precede the reduction over the ranks; the feature gradients stay partial sums of the band.
     ``grad_occ_full`` (N,S,S) with ``rows``: the same owner mode fed by the dense plane of the occupancy gradient alone
     (``dss_render_backward_owned_plane``) -- what the ranks of a step with a band-local loss all-gather (`gather_rows`)."""
-    lib = _lib.load()
     grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
     dev = grad_out.device
     idx = _lib.require_gpu(idx, "idx", _i32)
-    qvalue = _lib.require_gpu(qvalue, "qvalue", _f32)
-    scaler = _lib.require_gpu(scaler, "scaler", _f32)
-    points = _lib.require_gpu(points, "points", _f32)
-    radii = _lib.require_gpu(radii, "radii", _f32)
-    vis = _lib.require_gpu(_as_u8(visible), "visible", _u8)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    qvalue, scaler, points, radii = _gpu(_f32, qvalue=qvalue, scaler=scaler, points=points, radii=radii)
+    vis = _flags(visible, "visible")
+    first, num, _ = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     if wsum is not None:
         wsum = _lib.require_gpu(wsum, "wsum", _f32)
     N, H, W, K = idx.shape
@@ -604,11 +565,10 @@ def render_backward(grad_out, idx, qvalue, wsum, scaler, points, radii, visible,
     row0, row1, cyc = _band(rows, S)
     if W != S or H != band_rows(row0, row1, cyc) or tuple(grad_out.shape[:3]) != (N, H, W):
         raise RuntimeError("render_backward needs idx (N,rows,S,K) and grad_out (N,rows,S,C+1)")
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         if out is not None:  # caller-provided (P,C) / (P,3) float32 views, e.g. slices of one all-reduce bucket
             gf, gp = out
-            if tuple(gf.shape) != (P, C) or tuple(gp.shape) != (P, 3) or gf.dtype != _f32 or gp.dtype != _f32 \
-                    or not gf.is_contiguous() or not gp.is_contiguous():
+            if not (_dense(gf, (P, C)) and _dense(gp, (P, 3))):
                 raise RuntimeError("out must be contiguous float32 tensors of shape (P,C) and (P,3)")
         else:
             gf = torch.empty((P, C), dtype=_f32, device=dev) if with_features else None
@@ -624,73 +584,50 @@ def render_backward(grad_out, idx, qvalue, wsum, scaler, points, radii, visible,
             _lib.require_gpu(gather_only_rs, "gather_only_rs", _f32)
         if gather_only_rs is not None and out is None:
             raise RuntimeError("gather_only_rs needs out= (the gradients the full call zero-filled)")
-        w_p = m_p = None
+        # entry point by mode: the owner modes take the full-image gradient after grad_out and no projection
+        name, head, tail = "dss_render_backward", (grad_out,), (None, None)
         if project is not None:
-            w_t, m_t = _lib.require_gpu(project[0], "world", _f32), _lib.require_gpu(project[1], "M", _f32)
+            w_t, m_t = _gpu(_f32, world=project[0], M=project[1])
             if tuple(w_t.shape) != (P, 3) or tuple(m_t.shape) != (N, 4, 4):
                 raise RuntimeError("project=(world (P,3), M (N,4,4)) with P=%d N=%d, got %s %s"
                                    % (P, N, tuple(w_t.shape), tuple(m_t.shape)))
-            w_p, m_p = _lib.ptr(w_t), _lib.ptr(m_t)
-        ws = _lib.workspace(dev, lib.dss_render_backward_workspace(N, P, S))
-        # entry point by mode: the owner modes take the full-image gradient after grad_out and no projection
-        name, head, tail = "dss_render_backward", [_lib.ptr(grad_out)], [w_p, m_p]
+            tail = (w_t, m_t)
+        ws = _lib.workspace(dev, _lib.load().dss_render_backward_workspace(N, P, S))
         if grad_occ_full is not None:
             if project is not None or gather_only_rs is not None or grad_out_full is not None:
                 raise RuntimeError("grad_occ_full (owner mode of a band) excludes project=, gather_only_rs= and grad_out_full=")
             plane = _lib.require_gpu(grad_occ_full, "grad_occ_full", _f32)
             if tuple(plane.shape) != (N, S, S):
                 raise RuntimeError("grad_occ_full must be (N,S,S) = %s, got %s" % ((N, S, S), tuple(plane.shape)))
-            name, head, tail = "dss_render_backward_owned_plane", head + [_lib.ptr(plane)], []
+            name, head, tail = "dss_render_backward_owned_plane", (grad_out, plane), ()
         elif grad_out_full is not None:
             if project is not None or gather_only_rs is not None:
                 raise RuntimeError("grad_out_full (owner mode of a band) excludes project= and gather_only_rs=")
             full = _lib.require_gpu(grad_out_full, "grad_out_full", _f32)
             if tuple(full.shape) != (N, S, S, C + 1) or not full.is_contiguous():
                 raise RuntimeError("grad_out_full must be contiguous (N,S,S,C+1)")
-            name, head, tail = "dss_render_backward_owned", head + [_lib.ptr(full)], []
-        entry = getattr(lib, name if gather_only_rs is None else "dss_render_backward_gather")
-        rc = entry(*head, _lib.ptr(idx), _lib.ptr(qvalue), _lib.ptr(wsum), _lib.ptr(scaler), _lib.ptr(points),
-                   _lib.ptr(radii), _lib.ptr(vis), _lib.ptr(first), _lib.ptr(num), N, P, S, K, C, row0, row1, cyc,
-                   float(radii_s), float(clip), _lib.ptr(gf), _lib.ptr(gp), _lib.ptr(rs), *tail, _lib.ptr(ws), ws.numel(),
-                   _lib.stream_ptr(dev))
-    _lib.check(rc, name)
+            name, head, tail = "dss_render_backward_owned", (grad_out, full), ()
+        _lib.call(name if gather_only_rs is None else "dss_render_backward_gather", dev, *head, idx, qvalue, wsum, scaler,
+                  points, radii, vis, first, num, N, P, S, K, C, row0, row1, cyc, float(radii_s), float(clip), gf, gp, rs,
+                  *tail, ws, ws.numel())
     return (gf, gp, rs) if return_rs else (gf, gp)
 
 
 def gather_rows(src, row_pos, n_images: int, rows: int, row_floats: int, out=None):
     """``dss_gather_rows``: rows of an all-gathered (position, camera, row_floats) float32 buffer put in image order ->
     dense (n_images, rows, row_floats); ``row_pos`` int32 (rows,) = position of image row r in ``src``."""
-    lib = _lib.load()
     src = _lib.require_gpu(src, "src", _f32)
     dev = src.device
     row_pos = _lib.require_gpu(row_pos, "row_pos", _i32)
     if row_pos.numel() != rows or src.numel() % (n_images * row_floats):
         raise RuntimeError("gather_rows: row_pos must have %d entries and src whole (camera, row) slices" % rows)
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         if out is None:
             out = torch.empty((n_images, rows, row_floats), dtype=_f32, device=dev)
-        elif out.numel() != n_images * rows * row_floats or out.dtype != _f32 or not out.is_contiguous():
+        elif not _dense(out, n_images * rows * row_floats):
             raise RuntimeError("gather_rows: out must be a contiguous float32 tensor of %d elements" % (n_images * rows * row_floats))
-        rc = lib.dss_gather_rows(_lib.ptr(src), _lib.ptr(row_pos), int(n_images), int(rows), int(row_floats), _lib.ptr(out),
-                                 _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_gather_rows")
+        _lib.call("dss_gather_rows", dev, src, row_pos, int(n_images), int(rows), int(row_floats), out)
     return out
-
-
-class _NoSwitch:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_NO_SWITCH = _NoSwitch()
-
-
-def _on_device(dev):
-    """`torch.cuda.device(dev)` only when `dev` is not already the current device (the context manager costs ~5 us)"""
-    return _NO_SWITCH if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
 class FusedPlan:
@@ -804,36 +741,31 @@ class FusedPlan:
 
 
 def _aniso_args(vr6, frame_normals, Pw):
-    """(ptr(vr6), ptr(frame_normals)) of the anisotropic source variance, or (None, None)."""
+    """(vr6, frame_normals) of the anisotropic source variance, checked, or (None, None)."""
     if vr6 is None:
-        return None, None, None
-    vr6 = _lib.require_gpu(vr6, "vr6", _f32)
-    fn = _lib.require_gpu(frame_normals, "frame_normals", _f32)
+        return None, None
+    vr6, fn = _gpu(_f32, vr6=vr6, frame_normals=frame_normals)
     if tuple(vr6.shape) != (Pw, 6) or tuple(fn.shape) != (Pw, 3):
         raise RuntimeError("anisotropic mode needs vr6 (%d,6) and frame_normals (%d,3)" % (Pw, Pw))
-    return (vr6, fn), _lib.ptr(vr6), _lib.ptr(fn)
+    return vr6, fn
 
 
 def local_frames(points, knn_idx, cloud_to_packed_first_idx, num_points_per_cloud, return_curvature: bool = False):
     """PCA frames of the K-neighbourhoods (``knn_idx`` from ``knn_points``, self included) -> anisotropic source
     variance ``vr6 (P,6)`` (xx,xy,xz,yy,yz,zz) and frame normals ``(P,3)`` (rasterizer.py:256-291 +
     mathHelper.py:34-92 with neighborhood_size = 8)."""
-    lib = _lib.load()
     points = _lib.require_gpu(points, "points", _f32)
     dev = points.device
     knn_idx = _lib.require_gpu(knn_idx, "knn_idx", _i64)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     P, K = knn_idx.shape
     if points.shape[0] != P:
         raise RuntimeError("knn_idx must be (P,K) for the P packed points")
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         vr6 = torch.empty((P, 6), dtype=_f32, device=dev)
         fn = torch.empty((P, 3), dtype=_f32, device=dev)
         cv = torch.empty((P, 3), dtype=_f32, device=dev) if return_curvature else None
-        rc = lib.dss_local_frames(_lib.ptr(points), _lib.ptr(knn_idx), _lib.ptr(first), _lib.ptr(num), first.shape[0], P,
-                                  int(K), _lib.ptr(vr6), _lib.ptr(fn), _lib.ptr(cv), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_local_frames")
+        _lib.call("dss_local_frames", dev, points, knn_idx, first, num, N, P, int(K), vr6, fn, cv)
     return (vr6, fn, cv) if return_curvature else (vr6, fn)
 
 
@@ -847,45 +779,33 @@ def point_setup(world, normals, h, M, V, znear, zfar, cloud_to_packed_first_idx,
     ``pts_screen (P,3), ellipse_params (P,3), radii (P,2), scaler (P,), cutoff_threshold (P,),
     valid bool (P,)``.
     """
-    lib = _lib.load()
-    world = _lib.require_gpu(world, "world", _f32)
+    world, normals, h, M, V, znear, zfar = _gpu(_f32, world=world, normals=normals, h=h, M=M, V=V, znear=znear, zfar=zfar)
     dev = world.device
-    normals = _lib.require_gpu(normals, "normals", _f32)
-    h = _lib.require_gpu(h, "h", _f32)
-    M = _lib.require_gpu(M, "M", _f32)
-    V = _lib.require_gpu(V, "V", _f32)
-    znear = _lib.require_gpu(znear, "znear", _f32)
-    zfar = _lib.require_gpu(zfar, "zfar", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N, Pw = first.shape[0], world.shape[0]
-    if tuple(M.shape) != (N, 4, 4) or tuple(V.shape) != (N, 4, 4) or znear.numel() != N or zfar.numel() != N:
-        raise RuntimeError("camera tensors must be M,V (N,4,4) and znear,zfar (N,) with N=%d" % N)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    Pw = world.shape[0]
+    _check_cameras(M, V, znear, zfar, N)
     if normals.shape != world.shape:
         raise RuntimeError("normals must match world points")
     P = N * Pw if shared_cloud else Pw
-    per_point = h.numel() == Pw and not (h.numel() == N and Pw == N)
-    packed_h = (not per_point) and shared_cloud and N > 1 and h.numel() == P    # one value per (camera, point) pair
-    if not per_point and not packed_h and h.numel() != N:
-        raise RuntimeError("h must have %d (per point), %d (per cloud) or, for a shared cloud, %d (per packed point) entries" % (Pw, N, P))
-    with torch.cuda.device(dev):
-        out = dict(pts_screen=torch.empty((P, 3), dtype=_f32, device=dev),
-                   ellipse_params=torch.empty((P, 3), dtype=_f32, device=dev),
-                   radii=torch.empty((P, 2), dtype=_f32, device=dev),
-                   scaler=torch.empty((P,), dtype=_f32, device=dev),
-                   cutoff_threshold=torch.empty((P,), dtype=_f32, device=dev))
+    h_mode = _h_mode(h, N, Pw, P, shared_cloud)
+    with _on_device(dev):
+        e = lambda *shape: torch.empty(shape, dtype=_f32, device=dev)
+        out = dict(pts_screen=e(P, 3), ellipse_params=e(P, 3), radii=e(P, 2), scaler=e(P), cutoff_threshold=e(P))
         valid = torch.empty((P,), dtype=_u8, device=dev)
-        _keep, vr_p, fn_p = _aniso_args(vr6, frame_normals, Pw)
-        rc = lib.dss_point_setup(_lib.ptr(world), _lib.ptr(normals), _lib.ptr(h) if (per_point or packed_h) else None,
-                                 None if per_point else _lib.ptr(h), vr_p, fn_p, _lib.ptr(M), _lib.ptr(V), _lib.ptr(znear),
-                                 _lib.ptr(zfar), _lib.ptr(first), _lib.ptr(num), N, P, int(shared_cloud),
-                                 int(backface_culling), int(image_size), float(cutoff_threshold),
-                                 float(antialiasing_sigma), _lib.ptr(out["pts_screen"]),
-                                 _lib.ptr(out["ellipse_params"]), _lib.ptr(out["radii"]), _lib.ptr(out["scaler"]),
-                                 _lib.ptr(out["cutoff_threshold"]), _lib.ptr(valid), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_point_setup")
+        vr6, frame_normals = _aniso_args(vr6, frame_normals, Pw)
+        _lib.call("dss_point_setup", dev, world, normals, h if h_mode else None, None if h_mode == 1 else h, vr6,
+                  frame_normals, M, V, znear, zfar, first, num, N, P, int(shared_cloud), int(backface_culling),
+                  int(image_size), float(cutoff_threshold), float(antialiasing_sigma), *out.values(), valid)   # (`out` is in the entry's order)
     out["valid"] = valid.view(torch.bool)
     return out
+
+
+def _projection_inputs(world, M, V, cloud_to_packed_first_idx, num_points_per_cloud, grad_screen, valid):
+    """What `project_backward` and `camera_backward` share: the checked inputs, N, Pw and the device."""
+    world, M, V = _gpu(_f32, world=world, M=M, V=V)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    grad_screen = _lib.require_gpu(grad_screen, "grad_screen", _f32)
+    return world, M, V, first, num, grad_screen, _flags(valid, "valid"), N, world.shape[0], world.device
 
 
 def project_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_cloud, grad_screen, valid,
@@ -896,39 +816,26 @@ def project_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_clou
     launch (``dss_project_backward_features``) -> (grad_world (Pw,3), grad_features_world (Pw,C)).
     ``out`` = (grad_world, grad_features_world) to write into (contiguous float32, e.g. two views of one all-reduce
     buffer)."""
-    lib = _lib.load()
-    world = _lib.require_gpu(world, "world", _f32)
-    dev = world.device
-    M = _lib.require_gpu(M, "M", _f32)
-    V = _lib.require_gpu(V, "V", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    grad_screen = _lib.require_gpu(grad_screen, "grad_screen", _f32)
-    vis = _lib.require_gpu(_as_u8(valid), "valid", _u8)
-    N, Pw = first.shape[0], world.shape[0]
-    with torch.cuda.device(dev):
+    world, M, V, first, num, grad_screen, vis, N, Pw, dev = _projection_inputs(
+        world, M, V, cloud_to_packed_first_idx, num_points_per_cloud, grad_screen, valid)
+    with _on_device(dev):
         gw = torch.empty((Pw, 3), dtype=_f32, device=dev) if out is None else out[0]
-        if out is not None and (tuple(gw.shape) != (Pw, 3) or gw.dtype != _f32 or not gw.is_contiguous()):
+        if out is not None and not _dense(gw, (Pw, 3)):
             raise RuntimeError("out[0] must be a contiguous float32 (Pw,3) tensor")
-        if grad_features is not None:
-            gfeat = _lib.require_gpu(grad_features, "grad_features", _f32)
-            P = N * Pw if shared_cloud else Pw
-            if gfeat.dim() != 2 or gfeat.shape[0] != P:
-                raise RuntimeError("grad_features must be packed (P,C) with P=%d, got %s" % (P, tuple(gfeat.shape)))
-            C = gfeat.shape[1]
-            gfw = torch.empty((Pw, C), dtype=_f32, device=dev) if out is None else out[1]
-            if out is not None and (tuple(gfw.shape) != (Pw, C) or gfw.dtype != _f32 or not gfw.is_contiguous()):
-                raise RuntimeError("out[1] must be a contiguous float32 (Pw,C) tensor")
-            rc = lib.dss_project_backward_features(_lib.ptr(world), _lib.ptr(M), _lib.ptr(V), _lib.ptr(first), _lib.ptr(num), N,
-                                                   Pw, int(shared_cloud), _lib.ptr(grad_screen), _lib.ptr(vis), float(clip),
-                                                   _lib.ptr(gw), _lib.ptr(gfeat), C, _lib.ptr(gfw), _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_project_backward_features")
-            return gw, gfw
-        rc = lib.dss_project_backward(_lib.ptr(world), _lib.ptr(M), _lib.ptr(V), _lib.ptr(first), _lib.ptr(num), N,
-                                      Pw, int(shared_cloud), _lib.ptr(grad_screen), _lib.ptr(vis), float(clip),
-                                      _lib.ptr(gw), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_project_backward")
-    return gw
+        lead = (world, M, V, first, num, N, Pw, int(shared_cloud), grad_screen, vis, float(clip), gw)
+        if grad_features is None:
+            _lib.call("dss_project_backward", dev, *lead)
+            return gw
+        gfeat = _lib.require_gpu(grad_features, "grad_features", _f32)
+        P = N * Pw if shared_cloud else Pw
+        if gfeat.dim() != 2 or gfeat.shape[0] != P:
+            raise RuntimeError("grad_features must be packed (P,C) with P=%d, got %s" % (P, tuple(gfeat.shape)))
+        C = gfeat.shape[1]
+        gfw = torch.empty((Pw, C), dtype=_f32, device=dev) if out is None else out[1]
+        if out is not None and not _dense(gfw, (Pw, C)):
+            raise RuntimeError("out[1] must be a contiguous float32 (Pw,C) tensor")
+        _lib.call("dss_project_backward_features", dev, *lead, gfeat, C, gfw)
+    return gw, gfw
 
 
 def camera_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_cloud, grad_screen, valid,
@@ -936,37 +843,25 @@ def camera_backward(world, M, V, cloud_to_packed_first_idx, num_points_per_cloud
     """grad of (NDC x, NDC y, view z) w.r.t. the camera matrices (``dss_camera_backward``; the counterpart of
     `project_backward`, same inputs) -> (grad_M (N,4,4), grad_V (N,4,4)), fully written, bitwise reproducible.  From
     there plain torch autograd carries on to ``R``, ``T``, ``fov``, ... of the camera object."""
-    lib = _lib.load()
-    world = _lib.require_gpu(world, "world", _f32)
-    dev = world.device
-    M = _lib.require_gpu(M, "M", _f32)
-    V = _lib.require_gpu(V, "V", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    grad_screen = _lib.require_gpu(grad_screen, "grad_screen", _f32)
-    vis = _lib.require_gpu(_as_u8(valid), "valid", _u8)
-    N, Pw = first.shape[0], world.shape[0]
+    world, M, V, first, num, grad_screen, vis, N, Pw, dev = _projection_inputs(
+        world, M, V, cloud_to_packed_first_idx, num_points_per_cloud, grad_screen, valid)
     P = N * Pw if shared_cloud else Pw
     if tuple(M.shape) != (N, 4, 4) or tuple(V.shape) != (N, 4, 4) or tuple(grad_screen.shape) != (P, 3) or vis.numel() != P:
         raise RuntimeError("camera_backward: need M, V (N,4,4), grad_screen (P,3), valid (P,) with N=%d P=%d" % (N, P))
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         gM = torch.empty((N, 4, 4), dtype=_f32, device=dev)
         gV = torch.empty((N, 4, 4), dtype=_f32, device=dev)
-        ws = _lib.workspace(dev, lib.dss_camera_backward_workspace(N, P))
-        rc = lib.dss_camera_backward(_lib.ptr(world), _lib.ptr(M), _lib.ptr(V), _lib.ptr(first), _lib.ptr(num), N, Pw,
-                                     int(shared_cloud), _lib.ptr(grad_screen), _lib.ptr(vis), float(clip), _lib.ptr(gM),
-                                     _lib.ptr(gV), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_camera_backward")
+        ws = _lib.workspace(dev, _lib.load().dss_camera_backward_workspace(N, P))
+        _lib.call("dss_camera_backward", dev, world, M, V, first, num, N, Pw, int(shared_cloud), grad_screen, vis,
+                  float(clip), gM, gV, ws, ws.numel())
     return gM, gV
 
 
 def _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud):
-    """What the kNN entries share: the library, the three checked tensors, N, P and the device."""
-    lib = _lib.load()
+    """What the kNN entries share: the three checked tensors, N, P and the device."""
     points = _lib.require_gpu(points, "points", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    return lib, points, first, num, first.shape[0], points.shape[0], points.device
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    return points, first, num, N, points.shape[0], points.device
 
 
 def knn_kth_sqdist(points, cloud_to_packed_first_idx, num_points_per_cloud, K: int = 7, radius=None):
@@ -975,17 +870,14 @@ def knn_kth_sqdist(points, cloud_to_packed_first_idx, num_points_per_cloud, K: i
     variance-scale statistic (rasterizer.py:310-321, 366-383).  ``radius`` > 0 (``dss_knn_kth_sqdist_radius``): the
     fixed-radius semantics of the reference's DEFAULT search, ``frnn_grid_points(K, r = frnn_radius = 0.2)`` -- the largest of
     the K - 1 neighbour distances that lie within ``radius``, -1 for a point that has no neighbour there."""
-    lib, points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
-    with torch.cuda.device(dev):
+    points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
+    with _on_device(dev):
         out = torch.empty((P,), dtype=_f32, device=dev)
-        ws = _lib.workspace(dev, lib.dss_knn_workspace(N, P))
+        ws = _lib.workspace(dev, _lib.load().dss_knn_workspace(N, P))
         if radius is not None and radius > 0:
-            rc = lib.dss_knn_kth_sqdist_radius(_lib.ptr(points), _lib.ptr(first), _lib.ptr(num), N, P, int(K), float(radius),
-                                               _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+            _lib.call("dss_knn_kth_sqdist_radius", dev, points, first, num, N, P, int(K), float(radius), out, ws, ws.numel())
         else:
-            rc = lib.dss_knn_kth_sqdist(_lib.ptr(points), _lib.ptr(first), _lib.ptr(num), N, P, int(K), _lib.ptr(out),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_knn_kth_sqdist")
+            _lib.call("dss_knn_kth_sqdist", dev, points, first, num, N, P, int(K), out, ws, ws.numel())
     return out
 
 
@@ -993,31 +885,25 @@ def knn_points(points, cloud_to_packed_first_idx, num_points_per_cloud, K: int):
     """Self kNN of packed clouds -> (dists (P,K) squared, idx (P,K) int64 cloud-local), ascending, the point itself
     first, zero-padded for clouds with fewer than K points: the packed form of
     ``pytorch3d.ops.knn_points(p, p, lengths, lengths, K)`` used by the regularisers (losses.py:157-180)."""
-    lib, points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
-    with torch.cuda.device(dev):
+    points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
+    with _on_device(dev):
         dists = torch.empty((P, int(K)), dtype=_f32, device=dev)
         idx = torch.empty((P, int(K)), dtype=_i64, device=dev)
-        ws = _lib.workspace(dev, lib.dss_knn_workspace(N, P))
-        rc = lib.dss_knn_points(_lib.ptr(points), _lib.ptr(first), _lib.ptr(num), N, P, int(K), _lib.ptr(dists),
-                                _lib.ptr(idx), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_knn_points")
+        ws = _lib.workspace(dev, _lib.load().dss_knn_workspace(N, P))
+        _lib.call("dss_knn_points", dev, points, first, num, N, P, int(K), dists, idx, ws, ws.numel())
     return dists, idx
 
 
 def cloud_mean_clamp(values, cloud_to_packed_first_idx, num_points_per_cloud, scale: float, lo: float, hi: float,
                      fallback: float, min_points: int):
     """Per-cloud clamp(mean(values*scale), lo, hi) -> (N,), deterministic."""
-    lib = _lib.load()
     values = _lib.require_gpu(values, "values", _f32)
     dev = values.device
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    N = first.shape[0]
-    with torch.cuda.device(dev):
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    with _on_device(dev):
         out = torch.empty((N,), dtype=_f32, device=dev)
-        rc = lib.dss_cloud_mean_clamp(_lib.ptr(values), _lib.ptr(first), _lib.ptr(num), N, float(scale), float(lo),
-                                      float(hi), float(fallback), int(min_points), _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_cloud_mean_clamp")
+        _lib.call("dss_cloud_mean_clamp", dev, values, first, num, N, float(scale), float(lo), float(hi), float(fallback),
+                  int(min_points), out)
     return out
 
 
@@ -1027,27 +913,19 @@ def renderable_mean_clamp(values, world, V, znear, zfar, cloud_to_packed_first_i
     the mean over the points it keeps (view z in [znear, zfar]), divided by the LARGEST kept count of the batch like the
     reference's mean over the padded clouds (rasterizer.py:183-217, 320-326) -> (N,).  ``values``: (Pw,) one per world point,
     or (N, Pw) per (camera, point) from `knn_kth_sqdist_view` (a shared cloud in the reference's exact order)."""
-    lib = _lib.load()
-    values = _lib.require_gpu(values, "values", _f32)
+    values, world, V, znear, zfar = _gpu(_f32, values=values, world=world, V=V, znear=znear, zfar=zfar)
     dev = values.device
-    world = _lib.require_gpu(world, "world", _f32)
-    V = _lib.require_gpu(V, "V", _f32)
-    znear = _lib.require_gpu(znear, "znear", _f32)
-    zfar = _lib.require_gpu(zfar, "zfar", _f32)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, n_clouds = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     N, Pw = V.shape[0], world.shape[0]
     per_cam = values.dim() == 2
-    if (tuple(values.shape) != ((N, Pw) if per_cam else (Pw,))) or first.shape[0] != N or znear.numel() != N or zfar.numel() != N:
+    if (tuple(values.shape) != ((N, Pw) if per_cam else (Pw,))) or n_clouds != N or znear.numel() != N or zfar.numel() != N:
         raise RuntimeError("renderable_mean_clamp: values (Pw,) or (N,Pw); V, znear, zfar, first_idx, num_points per camera")
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         out = torch.empty((N,), dtype=_f32, device=dev)
         ws = _lib.workspace(dev, 512 * N)
-        rc = lib.dss_renderable_mean_clamp(_lib.ptr(values), _lib.ptr(world), _lib.ptr(V), _lib.ptr(znear), _lib.ptr(zfar),
-                                           _lib.ptr(first), _lib.ptr(num), N, int(shared_cloud), float(scale), float(lo),
-                                           float(hi), float(fallback), int(min_points), Pw if per_cam else 0, _lib.ptr(out),
-                                           _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_renderable_mean_clamp")
+        _lib.call("dss_renderable_mean_clamp", dev, values, world, V, znear, zfar, first, num, N, int(shared_cloud),
+                  float(scale), float(lo), float(hi), float(fallback), int(min_points), Pw if per_cam else 0, out,
+                  ws, ws.numel())
     return out
 
 
@@ -1058,60 +936,53 @@ def knn_kth_sqdist_view(points, cloud_to_packed_first_idx, num_points_per_cloud,
     one cloud, N cameras -> (N, P) (row c: among the points camera c keeps; 0 for the ones it drops); else cloud n belongs to
     camera n -> (P,).  Packed slots outside every cloud (before ``first_idx[0]``, between clouds, behind the last one) are 0,
     in every row."""
-    lib, points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
-    V = _lib.require_gpu(V, "V", _f32)
-    znear = _lib.require_gpu(znear, "znear", _f32)
-    zfar = _lib.require_gpu(zfar, "zfar", _f32)
+    points, first, num, N, P, dev = _knn_inputs(points, cloud_to_packed_first_idx, num_points_per_cloud)
+    V, znear, zfar = _gpu(_f32, V=V, znear=znear, zfar=zfar)
     n_cams = V.shape[0]
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         out = torch.empty((n_cams, P) if shared_cloud else (P,), dtype=_f32, device=dev)
-        ws = _lib.workspace(dev, lib.dss_knn_workspace(N, P))
-        rc = lib.dss_knn_kth_sqdist_view(_lib.ptr(points), _lib.ptr(first), _lib.ptr(num), N, P, int(K),
-                                         float(radius) if radius is not None else -1.0, _lib.ptr(V), _lib.ptr(znear),
-                                         _lib.ptr(zfar), n_cams, int(shared_cloud), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_knn_kth_sqdist_view")
+        ws = _lib.workspace(dev, _lib.load().dss_knn_workspace(N, P))
+        _lib.call("dss_knn_kth_sqdist_view", dev, points, first, num, N, P, int(K),
+                  float(radius) if radius is not None else -1.0, V, znear, zfar, n_cams, int(shared_cloud), out,
+                  ws, ws.numel())
     return out
 
 
 def _phong_common(world, normals, rgb, first, num, shared_cloud, ambient, diffuse_color, specular_color, light_vec,
-                  cam_center):
-    world = _lib.require_gpu(world, "world", _f32)
-    normals = _lib.require_gpu(normals, "normals", _f32)
-    rgb = _lib.require_gpu(rgb, "rgb", _f32)
-    first = _lib.require_gpu(first, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num, "num_points_per_cloud", _i64)
-    N, Pw = first.shape[0], world.shape[0]
+                  point_lights, cam_center, shininess, grad_out=None, who=None):
+    """What the four Phong operators share -> (dev, N, Pw, P, L, lead): the checked inputs as the argument list that every
+    one of their entries begins with (the backward entries after `grad_out`, checked here under the operator's name `who`)."""
+    world, normals, rgb = _gpu(_f32, world=world, normals=normals, rgb=rgb)
+    first, num, N = _ranges(first, num)
+    Pw = world.shape[0]
     P = N * Pw if shared_cloud else Pw
-    amb = _lib.require_gpu(ambient, "ambient", _f32)
-    kd = _lib.require_gpu(diffuse_color, "diffuse_color", _f32)
-    ks = _lib.require_gpu(specular_color, "specular_color", _f32)
-    lv = _lib.require_gpu(light_vec, "light_vec", _f32)
-    cam = _lib.require_gpu(cam_center, "cam_center", _f32)
+    amb, kd, ks, lv, cam = _gpu(_f32, ambient=ambient, diffuse_color=diffuse_color, specular_color=specular_color,
+                                light_vec=light_vec, cam_center=cam_center)
     L = kd.shape[1] if kd.dim() == 3 else 0
     if tuple(rgb.shape) != (P, 3) or normals.shape != world.shape or tuple(amb.shape) != (N, 3) \
             or tuple(kd.shape) != (N, L, 3) or tuple(ks.shape) != (N, L, 3) or tuple(lv.shape) != (N, L, 3) \
             or tuple(cam.shape) != (N, 3):
         raise RuntimeError("phong: need rgb (P,3), ambient / cam_center (N,3), light tensors (N,L,3)")
-    return world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L
+    lead = (world, normals, rgb, first, num, N, Pw, int(shared_cloud), amb, kd, ks, lv, L, int(point_lights), cam,
+            float(shininess))
+    if who is not None:
+        grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
+        if tuple(grad_out.shape) != (P, 3):
+            raise RuntimeError("%s: grad_out must be (P,3)" % who)
+        lead = (grad_out,) + lead
+    return world.device, N, Pw, P, L, lead
 
 
 def phong_forward(world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, ambient, diffuse_color,
                   specular_color, light_vec, point_lights: bool, cam_center, shininess: float = 64.0,
                   shared_cloud: bool = False):
     """Phong shading of the points (LightingTexture.forward, texture.py:65-125; lighting.py:10-172) -> (P,3)."""
-    lib = _lib.load()
-    world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L = _phong_common(
+    dev, N, Pw, P, L, lead = _phong_common(
         world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
-        specular_color, light_vec, cam_center)
-    dev = world.device
-    with torch.cuda.device(dev):
+        specular_color, light_vec, point_lights, cam_center, shininess)
+    with _on_device(dev):
         out = torch.empty((P, 3), dtype=_f32, device=dev)
-        rc = lib.dss_phong_forward(_lib.ptr(world), _lib.ptr(normals), _lib.ptr(rgb), _lib.ptr(first), _lib.ptr(num), N, Pw,
-                                   int(shared_cloud), _lib.ptr(amb), _lib.ptr(kd), _lib.ptr(ks), _lib.ptr(lv), L,
-                                   int(point_lights), _lib.ptr(cam), float(shininess), _lib.ptr(out),
-                                   _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_phong_forward")
+        _lib.call("dss_phong_forward", dev, *lead, out)
     return out
 
 
@@ -1119,23 +990,14 @@ def phong_backward(grad_out, world, normals, rgb, cloud_to_packed_first_idx, num
                    diffuse_color, specular_color, light_vec, point_lights: bool, cam_center, shininess: float = 64.0,
                    shared_cloud: bool = False):
     """-> (grad_world (Pw,3), grad_normals (Pw,3), grad_rgb (P,3))."""
-    lib = _lib.load()
-    world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L = _phong_common(
+    dev, N, Pw, P, L, lead = _phong_common(
         world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
-        specular_color, light_vec, cam_center)
-    grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
-    if tuple(grad_out.shape) != (P, 3):
-        raise RuntimeError("phong_backward: grad_out must be (P,3)")
-    dev = world.device
-    with torch.cuda.device(dev):
+        specular_color, light_vec, point_lights, cam_center, shininess, grad_out, "phong_backward")
+    with _on_device(dev):
         gw = torch.empty((Pw, 3), dtype=_f32, device=dev)
         gn = torch.empty((Pw, 3), dtype=_f32, device=dev)
         gc = torch.empty((P, 3), dtype=_f32, device=dev)
-        rc = lib.dss_phong_backward(_lib.ptr(grad_out), _lib.ptr(world), _lib.ptr(normals), _lib.ptr(rgb), _lib.ptr(first),
-                                    _lib.ptr(num), N, Pw, int(shared_cloud), _lib.ptr(amb), _lib.ptr(kd), _lib.ptr(ks),
-                                    _lib.ptr(lv), L, int(point_lights), _lib.ptr(cam), float(shininess), _lib.ptr(gw),
-                                    _lib.ptr(gn), _lib.ptr(gc), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_phong_backward")
+        _lib.call("dss_phong_backward", dev, *lead, gw, gn, gc)
     return gw, gn, gc
 
 
@@ -1144,22 +1006,13 @@ def phong_backward_camera(grad_out, world, normals, rgb, cloud_to_packed_first_i
                           shared_cloud: bool = False):
     """-> grad_cam (N,3): the shading's gradient w.r.t. the camera centres (``dss_phong_backward_camera``; same inputs as
     `phong_backward`), bitwise reproducible."""
-    lib = _lib.load()
-    world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L = _phong_common(
+    dev, N, Pw, P, L, lead = _phong_common(
         world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
-        specular_color, light_vec, cam_center)
-    grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
-    if tuple(grad_out.shape) != (P, 3):
-        raise RuntimeError("phong_backward_camera: grad_out must be (P,3)")
-    dev = world.device
-    with torch.cuda.device(dev):
+        specular_color, light_vec, point_lights, cam_center, shininess, grad_out, "phong_backward_camera")
+    with _on_device(dev):
         gcam = torch.empty((N, 3), dtype=_f32, device=dev)
-        ws = _lib.workspace(dev, lib.dss_camera_backward_workspace(N, P))
-        rc = lib.dss_phong_backward_camera(_lib.ptr(grad_out), _lib.ptr(world), _lib.ptr(normals), _lib.ptr(rgb),
-                                           _lib.ptr(first), _lib.ptr(num), N, Pw, int(shared_cloud), _lib.ptr(amb),
-                                           _lib.ptr(kd), _lib.ptr(ks), _lib.ptr(lv), L, int(point_lights), _lib.ptr(cam),
-                                           float(shininess), _lib.ptr(gcam), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_phong_backward_camera")
+        ws = _lib.workspace(dev, _lib.load().dss_camera_backward_workspace(N, P))
+        _lib.call("dss_phong_backward_camera", dev, *lead, gcam, ws, ws.numel())
     return gcam
 
 
@@ -1169,24 +1022,14 @@ def phong_backward_lights(grad_out, world, normals, rgb, cloud_to_packed_first_i
     """-> (grad_ambient (N,3), grad_diffuse, grad_specular, grad_light_vec (N,L,3)): the shading's gradient w.r.t. the
     lights (``dss_phong_backward_lights``; same inputs as `phong_backward`), bitwise reproducible.  ``ambient`` is the
     (N,3) sum over lights, and so is its gradient.  ``needs``: the outputs to compute; the others are returned as None."""
-    lib = _lib.load()
-    world, normals, rgb, first, num, N, Pw, P, amb, kd, ks, lv, cam, L = _phong_common(
+    dev, N, Pw, P, L, lead = _phong_common(
         world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
-        specular_color, light_vec, cam_center)
-    grad_out = _lib.require_gpu(grad_out, "grad_out", _f32)
-    if tuple(grad_out.shape) != (P, 3):
-        raise RuntimeError("phong_backward_lights: grad_out must be (P,3)")
-    dev = world.device
-    with torch.cuda.device(dev):
+        specular_color, light_vec, point_lights, cam_center, shininess, grad_out, "phong_backward_lights")
+    with _on_device(dev):
         outs = [torch.empty(shape, dtype=_f32, device=dev) if need else None
                 for need, shape in zip(needs, ((N, 3), (N, L, 3), (N, L, 3), (N, L, 3)))]
-        ws = _lib.workspace(dev, lib.dss_phong_backward_lights_workspace(N, P, L))
-        rc = lib.dss_phong_backward_lights(_lib.ptr(grad_out), _lib.ptr(world), _lib.ptr(normals), _lib.ptr(rgb),
-                                           _lib.ptr(first), _lib.ptr(num), N, Pw, int(shared_cloud), _lib.ptr(amb),
-                                           _lib.ptr(kd), _lib.ptr(ks), _lib.ptr(lv), L, int(point_lights), _lib.ptr(cam),
-                                           float(shininess), *[_lib.ptr(o) for o in outs], _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_phong_backward_lights")
+        ws = _lib.workspace(dev, _lib.load().dss_phong_backward_lights_workspace(N, P, L))
+        _lib.call("dss_phong_backward_lights", dev, *lead, *outs, ws, ws.numel())
     return tuple(outs)
 
 
@@ -1212,23 +1055,27 @@ def _knn_lists(knn_dists, knn_idx, P, need_dists=True):
     return knn_dists, knn_idx, int(knn_idx.shape[1])
 
 
+def _grad_loss(grad_loss, numel, shape_text):
+    """the optional upstream gradient of a per-point loss"""
+    if grad_loss is not None:
+        grad_loss = _lib.require_gpu(grad_loss, "grad_loss", _f32)
+        if grad_loss.numel() != numel:
+            raise RuntimeError("dss_amd: grad_loss must be %s" % shape_text)
+    return grad_loss
+
+
 def mollify_normals(normals, knn_dists, knn_idx, keep, cloud_to_packed_first_idx, num_points_per_cloud):
     """Robust normal mollification of the regularisers (SurfaceLoss._denoise_normals with get_phi weights,
     losses.py:181-222, 262-278) on the packed neighbour lists of :func:`knn_points` -> (P,3).  ``keep`` (P,) bool marks
     the points whose own normal is kept (visibility & inmask); None mollifies every point."""
-    lib = _lib.load()
     normals = _lib.require_gpu(normals, "normals", _f32)
     dev, P = normals.device, normals.shape[0]
     knn_dists, knn_idx, K = _knn_lists(knn_dists, knn_idx, P)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     keep = _mask_u8(keep, "keep", P, dev)
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         out = torch.empty_like(normals)
-        rc = lib.dss_mollify_normals(_lib.ptr(normals), _lib.ptr(knn_dists), _lib.ptr(knn_idx), _lib.ptr(keep),
-                                     _lib.ptr(first), _lib.ptr(num), first.shape[0], P, K, _lib.ptr(out),
-                                     _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_mollify_normals")
+        _lib.call("dss_mollify_normals", dev, normals, knn_dists, knn_idx, keep, first, num, N, P, K, out)
     return out
 
 
@@ -1236,53 +1083,45 @@ def projection_loss(points, mollified, knn_dists, knn_idx, visible, cloud_to_pac
                     sharpness_sigma: float, grad_loss=None, want_loss: bool = True, want_grad: bool = False):
     """ProjectionLoss.compute (losses.py:296-392) per packed point -> (loss (P,) or None, grad_points (P,3) or None);
     grad_points = d loss_i / d p_i * grad_loss_i (grad_loss None = ones)."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
-    mollified = _lib.require_gpu(mollified, "mollified", _f32)
+    points, mollified = _gpu(_f32, points=points, mollified=mollified)
     dev, P = points.device, points.shape[0]
     knn_dists, knn_idx, K = _knn_lists(knn_dists, knn_idx, P)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
     visible = _mask_u8(visible, "visible", P, dev)
-    if grad_loss is not None:
-        grad_loss = _lib.require_gpu(grad_loss, "grad_loss", _f32)
-        if grad_loss.numel() != P:
-            raise RuntimeError("dss_amd: grad_loss must be (P,)")
-    with torch.cuda.device(dev):
+    grad_loss = _grad_loss(grad_loss, P, "(P,)")
+    with _on_device(dev):
         loss = torch.empty((P,), dtype=_f32, device=dev) if want_loss else None
         grad = torch.empty((P, 3), dtype=_f32, device=dev) if want_grad else None
-        rc = lib.dss_projection_loss(_lib.ptr(points), _lib.ptr(mollified), _lib.ptr(knn_dists), _lib.ptr(knn_idx),
-                                     _lib.ptr(visible), _lib.ptr(first), _lib.ptr(num), first.shape[0], P, K,
-                                     float(sharpness_sigma), _lib.ptr(grad_loss), _lib.ptr(loss), _lib.ptr(grad),
-                                     _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_projection_loss")
+        _lib.call("dss_projection_loss", dev, points, mollified, knn_dists, knn_idx, visible, first, num, N, P, K,
+                  float(sharpness_sigma), grad_loss, loss, grad)
     return loss, grad
 
 
 def repulsion_loss(points, mollified, knn_idx, cloud_to_packed_first_idx, num_points_per_cloud, sharpness_sigma: float,
                    filter_scale: float, grad_loss=None, want_loss: bool = True, want_grad: bool = False):
     """RepulsionLoss.compute (losses.py:395-492) per packed point -> (loss (P,3) or None, grad_points (P,3) or None)."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
-    mollified = _lib.require_gpu(mollified, "mollified", _f32)
+    points, mollified = _gpu(_f32, points=points, mollified=mollified)
     dev, P = points.device, points.shape[0]
     _, knn_idx, K = _knn_lists(None, knn_idx, P, need_dists=False)
-    first = _lib.require_gpu(cloud_to_packed_first_idx, "cloud_to_packed_first_idx", _i64)
-    num = _lib.require_gpu(num_points_per_cloud, "num_points_per_cloud", _i64)
-    if grad_loss is not None:
-        grad_loss = _lib.require_gpu(grad_loss, "grad_loss", _f32)
-        if grad_loss.numel() != 3 * P:
-            raise RuntimeError("dss_amd: grad_loss must be (P,3)")
-    N = first.shape[0]
-    with torch.cuda.device(dev):
+    first, num, N = _ranges(cloud_to_packed_first_idx, num_points_per_cloud)
+    grad_loss = _grad_loss(grad_loss, 3 * P, "(P,3)")
+    with _on_device(dev):
         loss = torch.empty((P, 3), dtype=_f32, device=dev) if want_loss else None
         grad = torch.empty((P, 3), dtype=_f32, device=dev) if want_grad else None
         ws = _lib.workspace(dev, 24 * N)
-        rc = lib.dss_repulsion_loss(_lib.ptr(points), _lib.ptr(mollified), _lib.ptr(knn_idx), _lib.ptr(first), _lib.ptr(num),
-                                    N, P, K, float(sharpness_sigma), float(filter_scale), _lib.ptr(grad_loss), _lib.ptr(loss),
-                                    _lib.ptr(grad), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_repulsion_loss")
+        _lib.call("dss_repulsion_loss", dev, points, mollified, knn_idx, first, num, N, P, K, float(sharpness_sigma),
+                  float(filter_scale), grad_loss, loss, grad, ws, ws.numel())
     return loss, grad
+
+
+def _check_target_rgb(target_rgb):
+    if not isinstance(target_rgb, torch.Tensor) or not target_rgb.is_cuda or target_rgb.dtype != _f32:
+        raise RuntimeError("dss_amd: target_rgb must be a float32 GPU tensor (no CPU fallback)")
+
+
+def _grad_total(grad_total):
+    """the optional device scalar that scales an image-loss gradient -> float32 (1,) or None"""
+    return None if grad_total is None else _lib.require_gpu(grad_total, "grad_total", _f32).reshape(1)
 
 
 def _image_loss_args(rgba, target_rgb, target_mask):
@@ -1290,8 +1129,7 @@ def _image_loss_args(rgba, target_rgb, target_mask):
     if rgba.dim() != 4 or rgba.shape[-1] != 4:
         raise RuntimeError("dss_amd: rgba must be (N,H,W,4), got %s" % (tuple(rgba.shape),))
     N, H, W, _ = rgba.shape
-    if not isinstance(target_rgb, torch.Tensor) or not target_rgb.is_cuda or target_rgb.dtype != _f32:
-        raise RuntimeError("dss_amd: target_rgb must be a float32 GPU tensor (no CPU fallback)")
+    _check_target_rgb(target_rgb)
     if tuple(target_rgb.shape) != (N, H, W, 3):
         raise RuntimeError("dss_amd: target_rgb must be (N,H,W,3) = %s (a permuted NCHW view is fine), got %s"
                            % ((N, H, W, 3), tuple(target_rgb.shape)))
@@ -1303,39 +1141,30 @@ def image_loss_forward(rgba, target_rgb, target_mask, lambda_rgb: float, lambda_
     """Trainer.calc_dr_loss (trainer.py:332-372) on the rendered (N,H,W,4) image -> (losses (4,) = total, weighted rgb
     term, weighted silhouette term, IoU term; sums (N+1,5) float64 for :func:`image_loss_backward`).  ``target_rgb``
     (N,H,W,3) may be any strided view (e.g. ``img.permute(0, 2, 3, 1)``); no host synchronisation."""
-    lib = _lib.load()
     rgba, target_rgb, target_mask, N, H, W = _image_loss_args(rgba, target_rgb, target_mask)
     dev = rgba.device
-    sn, sh, sw, sc = target_rgb.stride()
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         losses = torch.empty((4,), dtype=_f32, device=dev)
-        sums = torch.empty((N + 1, 5), dtype=torch.float64, device=dev)
-        ws = _lib.workspace(dev, lib.dss_image_loss_workspace(N, H, W))
-        rc = lib.dss_image_loss_forward(_lib.ptr(rgba), _lib.ptr(target_rgb), sn, sh, sw, sc, _lib.ptr(target_mask), N, H, W,
-                                        float(lambda_rgb), float(lambda_silhouette), _lib.ptr(sums), _lib.ptr(losses),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_image_loss_forward")
+        sums = torch.empty((N + 1, 5), dtype=_f64, device=dev)
+        ws = _lib.workspace(dev, _lib.load().dss_image_loss_workspace(N, H, W))
+        _lib.call("dss_image_loss_forward", dev, rgba, target_rgb, *target_rgb.stride(), target_mask, N, H, W,
+                  float(lambda_rgb), float(lambda_silhouette), sums, losses, ws, ws.numel())
     return losses, sums
 
 
 def image_loss_backward(rgba, target_rgb, target_mask, lambda_rgb: float, lambda_silhouette: float, sums, grad_total=None):
     """Gradient of the total image loss w.r.t. the rendered image, (N,H,W,4), scaled by the device scalar
     ``grad_total`` (None = 1)."""
-    lib = _lib.load()
     rgba, target_rgb, target_mask, N, H, W = _image_loss_args(rgba, target_rgb, target_mask)
     dev = rgba.device
-    sums = _lib.require_gpu(sums, "sums", torch.float64)
+    sums = _lib.require_gpu(sums, "sums", _f64)
     if tuple(sums.shape) != (N + 1, 5):
         raise RuntimeError("dss_amd: sums must be (N+1,5) from image_loss_forward")
-    if grad_total is not None:
-        grad_total = _lib.require_gpu(grad_total, "grad_total", _f32).reshape(1)
-    sn, sh, sw, sc = target_rgb.stride()
-    with torch.cuda.device(dev):
+    grad_total = _grad_total(grad_total)
+    with _on_device(dev):
         grad = torch.empty_like(rgba)
-        rc = lib.dss_image_loss_backward(_lib.ptr(rgba), _lib.ptr(target_rgb), sn, sh, sw, sc, _lib.ptr(target_mask), N, H, W,
-                                         float(lambda_rgb), float(lambda_silhouette), _lib.ptr(sums), _lib.ptr(grad_total),
-                                         _lib.ptr(grad), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_image_loss_backward")
+        _lib.call("dss_image_loss_backward", dev, rgba, target_rgb, *target_rgb.stride(), target_mask, N, H, W,
+                  float(lambda_rgb), float(lambda_silhouette), sums, grad_total, grad)
     return grad
 
 
@@ -1343,9 +1172,7 @@ def points_inmask(points, M, mask_img, visible=None):
     """In-mask filter of the regularisers (point_modeling.py:183-208): bool (P,) = visible & any over the views of
     (target mask bilinearly sampled at the point's projection != 0).  ``points`` (P,3) world positions of one cloud,
     ``M`` (N,4,4) full projection matrices, ``mask_img`` (N,H,W) or (N,1,H,W)."""
-    lib = _lib.load()
-    points = _lib.require_gpu(points, "points", _f32)
-    M = _lib.require_gpu(M, "M", _f32)
+    points, M = _gpu(_f32, points=points, M=M)
     dev, P, N = points.device, points.shape[0], M.shape[0]
     if not isinstance(mask_img, torch.Tensor) or not mask_img.is_cuda:
         raise RuntimeError("dss_amd: mask_img must be a GPU tensor (no CPU fallback)")
@@ -1355,11 +1182,9 @@ def points_inmask(points, M, mask_img, visible=None):
         raise RuntimeError("dss_amd: mask_img must be (N,H,W) or (N,1,H,W) with N = %d views, got %s" % (N, tuple(mask_img.shape)))
     mask_img = mask_img.to(_f32).contiguous()
     visible = _mask_u8(visible, "visible", P, dev)
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         out = torch.empty((P,), dtype=torch.uint8, device=dev)
-        rc = lib.dss_points_inmask(_lib.ptr(points), _lib.ptr(M), _lib.ptr(mask_img), _lib.ptr(visible), N, P,
-                                   mask_img.shape[1], mask_img.shape[2], _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_points_inmask")
+        _lib.call("dss_points_inmask", dev, points, M, mask_img, visible, N, P, mask_img.shape[1], mask_img.shape[2], out)
     return out.view(torch.bool)   # the kernel writes 0 / 1
 
 
@@ -1382,7 +1207,7 @@ def band_targets(target_rgb, target_mask, rows):
     """The rows ``rows`` of the targets of a band loss, gathered ONCE (a tile-row-cyclic band costs two index_select launches
     per call otherwise): pass the result as ``band_targets=`` to `image_loss_band_sums` / `image_loss_band_backward` while the
     targets stay the same."""
-    row0, row1, cyc = _band(rows, None) if len(rows) > 2 else (int(rows[0]), int(rows[1]), 1)
+    row0, row1, cyc = _band(rows, None)
     N, H, W = target_rgb.shape[0], target_rgb.shape[1], target_rgb.shape[2]
     target_mask = target_mask.to(_f32).reshape(N, H, W)
     if cyc > 1:
@@ -1399,13 +1224,12 @@ def _band_args(rgba_band, target_rgb, target_mask, rows, band_targets=None, keep
     taken as it is (not made contiguous)."""
     if not keep_strides:
         rgba_band = _lib.require_gpu(rgba_band, "rgba_band", _f32)
-    row0, row1, cyc = _band(rows, None) if rows is not None and len(rows) > 2 else (int(rows[0]), int(rows[1]), 1)
+    row0, row1, cyc = _band(rows, None)
     want = band_rows(row0, row1, cyc)
     if rgba_band.dim() != 4 or rgba_band.shape[-1] != 4 or rgba_band.shape[1] != want:
         raise RuntimeError("dss_amd: rgba_band must be (N, %d, W, 4) for rows %s, got %s" % (want, tuple(rows), tuple(rgba_band.shape)))
     N, nr, W, _ = rgba_band.shape
-    if not isinstance(target_rgb, torch.Tensor) or not target_rgb.is_cuda or target_rgb.dtype != _f32:
-        raise RuntimeError("dss_amd: target_rgb must be a float32 GPU tensor (no CPU fallback)")
+    _check_target_rgb(target_rgb)
     H = target_rgb.shape[1]
     if target_rgb.dim() != 4 or tuple(target_rgb.shape) != (N, H, W, 3) or not (0 <= row0 <= row1 <= H):
         raise RuntimeError("dss_amd: target_rgb must be the full (N,H,W,3) target with 0 <= row0 <= row1 <= H")
@@ -1428,53 +1252,41 @@ def _band_args(rgba_band, target_rgb, target_mask, rows, band_targets=None, keep
 def image_loss_band_sums(rgba_band, target_rgb, target_mask, rows, band_targets=None):
     """Per-image sums of ``Trainer.calc_dr_loss`` over the row band ``rows = (row0, row1)`` -> float64 (N+1,5) whose
     first N rows are filled; all-reduce (SUM) ``sums[:N]`` over the ranks, then :func:`image_loss_from_sums`."""
-    lib = _lib.load()
     rgba_band, band_rgb, band_mask, _keep, N, nr, W, H, mstride = _band_args(rgba_band, target_rgb, target_mask, rows, band_targets)
     dev = rgba_band.device
-    with torch.cuda.device(dev):
-        sums = torch.zeros((N + 1, 5), dtype=torch.float64, device=dev)
+    with _on_device(dev):
+        sums = torch.zeros((N + 1, 5), dtype=_f64, device=dev)
         if nr > 0:
-            sn, sh, sw, sc = band_rgb.stride()
-            ws = _lib.workspace(dev, lib.dss_image_loss_workspace(N, nr, W))
-            rc = lib.dss_image_loss_band_sums(_lib.ptr(rgba_band), _lib.ptr(band_rgb), sn, sh, sw, sc,
-                                              _lib.ptr(band_mask), mstride, N, nr, W, _lib.ptr(sums),
-                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_image_loss_band_sums")
+            ws = _lib.workspace(dev, _lib.load().dss_image_loss_workspace(N, nr, W))
+            _lib.call("dss_image_loss_band_sums", dev, rgba_band, band_rgb, *band_rgb.stride(), band_mask, mstride, N, nr, W,
+                      sums, ws, ws.numel())
     return sums
 
 
 def image_loss_from_sums(sums, image_size, lambda_rgb: float, lambda_silhouette: float):
     """Totals row + losses (4,) from the (all-reduced) per-image sums; ``image_size = (H, W)`` of the FULL image."""
-    lib = _lib.load()
-    sums = _lib.require_gpu(sums, "sums", torch.float64)
+    sums = _lib.require_gpu(sums, "sums", _f64)
     N = sums.shape[0] - 1
     dev = sums.device
-    with torch.cuda.device(dev):
+    with _on_device(dev):
         losses = torch.empty((4,), dtype=_f32, device=dev)
-        rc = lib.dss_image_loss_from_sums(_lib.ptr(sums), N, int(image_size[0]), int(image_size[1]), float(lambda_rgb),
-                                          float(lambda_silhouette), _lib.ptr(losses), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_image_loss_from_sums")
+        _lib.call("dss_image_loss_from_sums", dev, sums, N, int(image_size[0]), int(image_size[1]), float(lambda_rgb),
+                  float(lambda_silhouette), losses)
     return losses
 
 
 def image_loss_band_backward(rgba_band, target_rgb, target_mask, rows, lambda_rgb: float, lambda_silhouette: float, sums,
                              grad_total=None, band_targets=None):
     """The band ``rows`` of d total / d rgba, (N,rows,W,4), from the reduced ``sums`` (after image_loss_from_sums)."""
-    lib = _lib.load()
     rgba_band, band_rgb, band_mask, _keep, N, nr, W, H, mstride = _band_args(rgba_band, target_rgb, target_mask, rows, band_targets)
     dev = rgba_band.device
-    sums = _lib.require_gpu(sums, "sums", torch.float64)
-    if grad_total is not None:
-        grad_total = _lib.require_gpu(grad_total, "grad_total", _f32).reshape(1)
-    with torch.cuda.device(dev):
+    sums = _lib.require_gpu(sums, "sums", _f64)
+    grad_total = _grad_total(grad_total)
+    with _on_device(dev):
         grad = torch.empty_like(rgba_band)
         if nr > 0:
-            sn, sh, sw, sc = band_rgb.stride()
-            rc = lib.dss_image_loss_band_backward(_lib.ptr(rgba_band), _lib.ptr(band_rgb), sn, sh, sw, sc,
-                                                  _lib.ptr(band_mask), mstride, N, nr, W, H,
-                                                  float(lambda_rgb), float(lambda_silhouette), _lib.ptr(sums),
-                                                  _lib.ptr(grad_total), _lib.ptr(grad), _lib.stream_ptr(dev))
-            _lib.check(rc, "dss_image_loss_band_backward")
+            _lib.call("dss_image_loss_band_backward", dev, rgba_band, band_rgb, *band_rgb.stride(), band_mask, mstride,
+                      N, nr, W, H, float(lambda_rgb), float(lambda_silhouette), sums, grad_total, grad)
     return grad
 
 
@@ -1499,20 +1311,17 @@ def image_loss_band_partials(rgba_band, target_rgb, target_mask, rows, band_targ
     per-image sums -> float64 (N, 64, 5).  All-reduce THEM (SUM) over the ranks, then `image_loss_band_backward_partials`.
     ``rgba_band`` may be the strided (N, rows, W, 4) view of a (row, camera, col, channel) buffer (no copy).
     ``out``: a caller-owned buffer of that shape (a step that replays as a graph all-reduces a static one)."""
-    lib = _lib.load()
     view, rsn, rsh = _strided_band(rgba_band)
     _c, band_rgb, band_mask, _keep, N, nr, W, H, mstride = _band_args(view, target_rgb, target_mask, rows, band_targets,
                                                                       keep_strides=True)
     dev = view.device
-    with torch.cuda.device(dev):
-        n = lib.dss_image_loss_band_partials_count(N)
-        part = torch.empty((N, n // (5 * N), 5), dtype=torch.float64, device=dev) if out is None else out
-        if part.numel() != n or part.dtype != torch.float64 or not part.is_contiguous():
+    with _on_device(dev):
+        n = _lib.load().dss_image_loss_band_partials_count(N)
+        part = torch.empty((N, n // (5 * N), 5), dtype=_f64, device=dev) if out is None else out
+        if not _dense(part, n, _f64):
             raise RuntimeError("dss_amd: out must be a contiguous float64 tensor of %d elements" % n)
-        sn, sh, sw, sc = band_rgb.stride() if nr > 0 else (0, 0, 0, 0)
-        rc = lib.dss_image_loss_band_partials(_lib.ptr(view), _lib.ptr(band_rgb), sn, sh, sw, sc, _lib.ptr(band_mask), mstride,
-                                              N, nr, W, rsn, rsh, _lib.ptr(part), _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_image_loss_band_partials")
+        strides = band_rgb.stride() if nr > 0 else (0, 0, 0, 0)
+        _lib.call("dss_image_loss_band_partials", dev, view, band_rgb, *strides, band_mask, mstride, N, nr, W, rsn, rsh, part)
     return part
 
 
@@ -1522,29 +1331,25 @@ def image_loss_band_backward_partials(rgba_band, target_rgb, target_mask, rows, 
     weighted rgb term, weighted silhouette term, IoU term[, sums (N+1,5) float64]) -- identical bits on every rank.
     ``alpha_out`` (N, rows, W) float32, last dimension contiguous (any camera / row strides): receives the alpha channel of
     the gradient a second time -- the send buffer of the owner form's alpha-plane exchange, no extraction copy."""
-    lib = _lib.load()
     view, rsn, rsh = _strided_band(rgba_band)
     _c, band_rgb, band_mask, _keep, N, nr, W, H, mstride = _band_args(view, target_rgb, target_mask, rows, band_targets,
                                                                       keep_strides=True)
     dev = view.device
-    partials = _lib.require_gpu(partials, "partials", torch.float64)
-    if partials.numel() != lib.dss_image_loss_band_partials_count(N):
+    partials = _lib.require_gpu(partials, "partials", _f64)
+    if partials.numel() != _lib.load().dss_image_loss_band_partials_count(N):
         raise RuntimeError("dss_amd: partials must come from image_loss_band_partials")
-    if grad_total is not None:
-        grad_total = _lib.require_gpu(grad_total, "grad_total", _f32).reshape(1)
-    a_p, asn, ash = None, 0, 0
+    grad_total = _grad_total(grad_total)
+    asn, ash = 0, 0
     if alpha_out is not None:
         if tuple(alpha_out.shape) != (N, nr, W) or alpha_out.dtype != _f32 or not alpha_out.is_cuda or (nr > 0 and alpha_out.stride(2) != 1):
             raise RuntimeError("dss_amd: alpha_out must be a float32 GPU tensor (N,%d,%d) with contiguous rows" % (nr, W))
-        a_p, asn, ash = _lib.ptr(alpha_out), int(alpha_out.stride(0)), int(alpha_out.stride(1))
-    with torch.cuda.device(dev):
+        asn, ash = int(alpha_out.stride(0)), int(alpha_out.stride(1))
+    with _on_device(dev):
         grad = torch.empty((N, nr, W, 4), dtype=_f32, device=dev)
         losses = torch.empty((4,), dtype=_f32, device=dev)
-        sums = torch.empty((N + 1, 5), dtype=torch.float64, device=dev) if want_sums else None
-        sn, sh, sw, sc = band_rgb.stride() if nr > 0 else (0, 0, 0, 0)
-        rc = lib.dss_image_loss_band_backward_partials(_lib.ptr(view), _lib.ptr(band_rgb), sn, sh, sw, sc, _lib.ptr(band_mask),
-                                                       mstride, N, nr, W, H, float(lambda_rgb), float(lambda_silhouette),
-                                                       _lib.ptr(partials), _lib.ptr(grad_total), _lib.ptr(grad), _lib.ptr(losses),
-                                                       _lib.ptr(sums), rsn, rsh, a_p, asn, ash, _lib.stream_ptr(dev))
-    _lib.check(rc, "dss_image_loss_band_backward_partials")
+        sums = torch.empty((N + 1, 5), dtype=_f64, device=dev) if want_sums else None
+        strides = band_rgb.stride() if nr > 0 else (0, 0, 0, 0)
+        _lib.call("dss_image_loss_band_backward_partials", dev, view, band_rgb, *strides, band_mask, mstride, N, nr, W, H,
+                  float(lambda_rgb), float(lambda_silhouette), partials, grad_total, grad, losses, sums, rsn, rsh,
+                  alpha_out, asn, ash)
     return (grad, losses, sums) if want_sums else (grad, losses)

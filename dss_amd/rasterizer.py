@@ -606,11 +606,11 @@ class SurfaceSplatting(torch.nn.Module):
                 a["znear"].numel() != N or a["zfar"].numel() != N or a["first_idx"].numel() != N:
             return None
         P = N * Pw if a["shared"] else Pw
-        h = a["h"]
-        per_point = 1 if (h.numel() == Pw and not (h.numel() == N and Pw == N)) else 0
-        if not per_point and a["shared"] and N > 1 and h.numel() == P:
-            per_point = 2          # one value per (camera, point) pair
-        if feats.shape[0] != P or (not per_point and h.numel() != N) or P == 0:
+        if feats.shape[0] != P or P == 0:
+            return None
+        try:
+            per_point = ops._h_mode(a["h"], N, Pw, P, a["shared"])
+        except RuntimeError:   # (the general path raises it again, as the caller's error)
             return None
         key = (dev, N, Pw, P, int(st.image_size), int(st.points_per_pixel), feats.shape[1], bool(a["shared"]), per_point,
                a["vr6"] is not None, bool(st.backface_culling), float(st.cutoff_threshold), float(st.antialiasing_sigma),
