@@ -4,7 +4,8 @@ Drop-in for the hot path of yifita/DSS: ``dss_amd.rasterizer.SurfaceSplatting`` 
 ``PointsRasterizationSettings`` and ``dss_amd.renderer.SurfaceSplattingRenderer`` mirror
 ``DSS.core.rasterizer`` / ``DSS.core.renderer``; ``dss_amd.ops`` mirrors the native module
 ``DSS._C``.  All compute runs in hand-written HIP kernels behind the C ABI of
-``include/dss_hip.h`` (``dss_amd/csrc/libdss_hip.so``).
+``include/dss_hip.h`` (``dss_amd/csrc/libdss_hip.so``).  ``dss_amd.losses`` holds the regularisers, the image loss
+and ``chamfer_distance`` (the 3-D metric of ``Trainer.evaluate_3d``) on the same kernels.
 """
 __version__ = "0.1.0"
 

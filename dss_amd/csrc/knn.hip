@@ -1779,3 +1779,243 @@ extern "C" int dss_knn_kth_sqdist_view(const float *points, const int64_t *first
     return knn_run("dss_knn_kth_sqdist_view", points, first_idx, num_pts, N, P, K, kth_sqdist, nullptr, nullptr, workspace,
                    workspace_bytes, stream, radius, view);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Nearest point of ANOTHER cloud (dss_nearest_points) and the chamfer point term's gradient (dss_chamfer_backward): the
+// 3-D metric of the reference's loop, Trainer.evaluate_3d (DSS/training/trainer.py:144-171) =
+// pytorch3d.loss.chamfer_distance(target, model).  Every search above is a self query; here cloud n of x is searched
+// in cloud n of y.  The grid of the TARGET y is built by build_grid, unchanged (same KnnGrid, same counting sort); only
+// the query is new: one thread per query point of x, in input order, K = 1.
+//
+// Exactness.  The query's start cell is its position's cell CLAMPED into the target's grid (a query may lie outside the
+// target's bounding box).  Ring 1 visits the 3x3x3 block around it, ring r the shell that grows the block to
+// [c - r, c + r]^3, cut at the grid's sides.  Every point not yet visited lies in a cell beyond one of the block's faces
+// that has cells behind it -- on the low x side: cell index < cx - r, hence x < F = minx + (cx - r) cell -- AND inside
+// the grid's box [min, min + res cell] on the two other axes (the box holds every point: min is the clouds' own
+// minimum, res cell >= 1.0001 extent).  Its distance to the query at its REAL position q is therefore at least
+//     sqrt((qx - F)^2 + oy^2 + oz^2),     o = distance of q to the grid's box along that axis (0 when inside),
+// and the smallest of these over the (at most six) open faces bounds everything unvisited.  Inside the box this is the
+// self query's rule; outside, the `o` terms keep the bound close to the true distance, so a query 50 cells away stops
+// after the rings that cover its nearest face region instead of walking the whole grid.  Nothing guarantees a hit in
+// the first block: the best distance starts at +inf, empty rings go on until the bound passes it, and when no face is
+// open (at the latest ring = res) every cell has been visited.  Rounding: each term is reduced by
+// tol = 1e-6 (res cell + |q| + |min|) before it is squared, which exceeds the fp32 error of the cell assignment
+// ((v - min) inv_cell, ~5 ulp of res cell), of F and of the subtraction (1 ulp of |F| + |q|) several times over, so an
+// unvisited point's fp32 distance is strictly larger than the bound: the search stops at best <= bound^2 and an
+// unvisited point can neither beat the result nor tie with it.  Among the visited candidates the order is
+// (distance, id), the order of dss_knn_points: ties go to the smaller id whatever the cell order.  Distances are the
+// difference form of knn_query_kernel's `consider` ("dx = q.x - qx ... d2 = dx * dx + dy * dy + dz * dz", built with
+// -ffp-contract=off) on the world coordinates: (dx dx + dy dy) + dz dz, dx = x - y.
+// A query that compares with nothing (NaN position) reports (0, -1) like a query whose target cloud is empty.
+// ---------------------------------------------------------------------------------------------------------------
+namespace dss {
+
+__device__ __forceinline__ int nearest_start_cell(float v, float mn, float inv_cell, int res)
+{
+    // clamped as a float: the quotient of a far query (or of a degenerate grid, cell ~ 1e-12) does not fit an int
+    return (int)fminf(fmaxf(floorf((v - mn) * inv_cell), 0.0f), (float)(res - 1));
+}
+
+__global__ __launch_bounds__(256) void nearest_query_kernel(const float *__restrict__ x, const int64_t *__restrict__ x_first,
+                                                            const int64_t *__restrict__ x_num, int64_t Px,
+                                                            const int64_t *__restrict__ y_first, const int64_t *__restrict__ y_num,
+                                                            int N, const KnnGrid *__restrict__ grids, size_t stride,
+                                                            const uint32_t *__restrict__ offsets, const float4 *__restrict__ sorted,
+                                                            float *__restrict__ d2_out, int64_t *__restrict__ idx_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Px) return;
+    const int n = find_cloud(i, x_first, x_num, N);
+    if (n < 0 || y_num[n] <= 0) {   // slot of no cloud (its position is not read), or nothing to search
+        d2_out[i] = 0.0f;
+        idx_out[i] = -1;
+        return;
+    }
+    const KnnGrid g = grids[n];
+    const int64_t f0 = y_first[n];
+    const uint32_t *off = offsets + (size_t)n * stride;
+    const float qx = x[3 * i], qy = x[3 * i + 1], qz = x[3 * i + 2];
+    const int res = g.res;
+    const int cx = nearest_start_cell(qx, g.minx, g.inv_cell, res);
+    const int cy = nearest_start_cell(qy, g.miny, g.inv_cell, res);
+    const int cz = nearest_start_cell(qz, g.minz, g.inv_cell, res);
+    const float span = (float)res * g.cell;
+    const float tolx = 1e-6f * (span + fabsf(qx) + fabsf(g.minx)), toly = 1e-6f * (span + fabsf(qy) + fabsf(g.miny)),
+                tolz = 1e-6f * (span + fabsf(qz) + fabsf(g.minz));
+    // distance of the query to the grid's box along each axis, rounded down
+    const float ox = fmaxf(fmaxf(g.minx - qx, qx - (g.minx + span)) - tolx, 0.0f);
+    const float oy = fmaxf(fmaxf(g.miny - qy, qy - (g.miny + span)) - toly, 0.0f);
+    const float oz = fmaxf(fmaxf(g.minz - qz, qz - (g.minz + span)) - tolz, 0.0f);
+    const float ox2 = ox * ox, oy2 = oy * oy, oz2 = oz * oz;
+    float best = __builtin_huge_valf();
+    int bid = 0x7fffffff;
+    auto consider = [&](const float4 q) __attribute__((always_inline)) {
+        const float dx = qx - q.x, dy = qy - q.y, dz = qz - q.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const int id = __float_as_int(q.w);
+        const bool lt = (d2 < best) | ((d2 == best) & (id < bid));
+        best = lt ? d2 : best;
+        bid = lt ? id : bid;
+    };
+    // candidates [s, e) of the cell-sorted array, four per memory round trip (clamped loads: a repeated candidate
+    // changes nothing when K = 1)
+    auto visit = [&](uint32_t s, uint32_t e) __attribute__((always_inline)) {
+        for (uint32_t j = s; j < e; j += 4) {
+            const float4 q0 = sorted[f0 + j], q1 = sorted[f0 + min(j + 1, e - 1)], q2 = sorted[f0 + min(j + 2, e - 1)],
+                         q3 = sorted[f0 + min(j + 3, e - 1)];
+            consider(q0); consider(q1); consider(q2); consider(q3);
+        }
+    };
+    for (int ring = 1; ring <= res; ++ring) {
+        const int x0 = max(cx - ring, 0), x1 = min(cx + ring, res - 1);
+        const int y0 = max(cy - ring, 0), y1 = min(cy + ring, res - 1);
+        const int z0 = max(cz - ring, 0), z1 = min(cz + ring, res - 1);
+        for (int z = z0; z <= z1; ++z)
+            for (int y = y0; y <= y1; ++y) {
+                const int c = (z * res + y) * res;
+                // cells consecutive along x are consecutive in memory: a row of the first block, or of a y / z face of
+                // the shell, is ONE range; the other rows of a shell contribute their two end cells
+                if (ring == 1 || z == cz - ring || z == cz + ring || y == cy - ring || y == cy + ring) {
+                    visit(off[c + x0], off[c + x1 + 1]);
+                } else {
+                    if (cx - ring >= 0) visit(off[c + cx - ring], off[c + cx - ring + 1]);
+                    if (cx + ring < res) visit(off[c + cx + ring], off[c + cx + ring + 1]);
+                }
+            }
+        // squared distance from the query's real position to everything not visited (see the exactness note above)
+        float b2 = __builtin_huge_valf();
+        if (cx - ring > 0) { const float d = fmaxf(qx - (g.minx + (float)(cx - ring) * g.cell) - tolx, 0.0f); b2 = fminf(b2, d * d + oy2 + oz2); }
+        if (cx + ring < res - 1) { const float d = fmaxf((g.minx + (float)(cx + ring + 1) * g.cell) - qx - tolx, 0.0f); b2 = fminf(b2, d * d + oy2 + oz2); }
+        if (cy - ring > 0) { const float d = fmaxf(qy - (g.miny + (float)(cy - ring) * g.cell) - toly, 0.0f); b2 = fminf(b2, d * d + ox2 + oz2); }
+        if (cy + ring < res - 1) { const float d = fmaxf((g.miny + (float)(cy + ring + 1) * g.cell) - qy - toly, 0.0f); b2 = fminf(b2, d * d + ox2 + oz2); }
+        if (cz - ring > 0) { const float d = fmaxf(qz - (g.minz + (float)(cz - ring) * g.cell) - tolz, 0.0f); b2 = fminf(b2, d * d + ox2 + oy2); }
+        if (cz + ring < res - 1) { const float d = fmaxf((g.minz + (float)(cz + ring + 1) * g.cell) - qz - tolz, 0.0f); b2 = fminf(b2, d * d + ox2 + oy2); }
+        if (b2 == __builtin_huge_valf() || best <= b2) break;
+    }
+    const bool found = bid != 0x7fffffff;
+    d2_out[i] = found ? best : 0.0f;
+    idx_out[i] = found ? (int64_t)bid - f0 : -1;
+}
+
+// Gradient of the chamfer point term for ONE point i of cloud set a (x or y) against set b, the index lists constant:
+//     grad_a[i] = 2 ga[i] (a_i - b_nn(i))  +  sum over the points j of b whose nearest point is i of  2 gb[j] (a_i - b_j).
+// The sum is many-to-one.  No atomics: order_ba lists b's packed ids sorted by (packed id of their nearest point in a, own
+// id), so the contributors of i are one contiguous segment; the thread finds its start by binary search and adds the
+// segment front to back, in double, rounding once -- the same bits on every run.  Pairs with idx < 0, and slots of no
+// cloud, sort behind every real target and contribute nothing.
+__device__ __forceinline__ int64_t chamfer_target(int64_t j, const int64_t *__restrict__ b_first, const int64_t *__restrict__ b_num,
+                                                  const int64_t *__restrict__ a_first, int N, int64_t Pb,
+                                                  const int64_t *__restrict__ idx_ba)
+{
+    if ((uint64_t)j >= (uint64_t)Pb) return 0x7fffffffffffffffll;
+    const int m = find_cloud(j, b_first, b_num, N);
+    const int64_t t = idx_ba[j];
+    return (m < 0 || t < 0) ? 0x7fffffffffffffffll : a_first[m] + t;
+}
+
+__device__ __forceinline__ void chamfer_grad_point(int64_t i, const float *__restrict__ a, const float *__restrict__ b,
+                                                   const int64_t *__restrict__ a_first, const int64_t *__restrict__ a_num,
+                                                   const int64_t *__restrict__ b_first, const int64_t *__restrict__ b_num, int N,
+                                                   int64_t Pb, const int64_t *__restrict__ idx_ab, const int64_t *__restrict__ idx_ba,
+                                                   const int64_t *__restrict__ order_ba, const float *__restrict__ ga,
+                                                   const float *__restrict__ gb, float *__restrict__ grad_a)
+{
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const int n = find_cloud(i, a_first, a_num, N);
+    if (n >= 0) {
+        const double ax = (double)a[3 * i], ay = (double)a[3 * i + 1], az = (double)a[3 * i + 2];
+        const int64_t t = idx_ab[i];
+        const int64_t jn = b_first[n] + t;
+        if (t >= 0 && jn < Pb) {
+            const double w = 2.0 * (double)ga[i];
+            s0 = w * (ax - (double)b[3 * jn]); s1 = w * (ay - (double)b[3 * jn + 1]); s2 = w * (az - (double)b[3 * jn + 2]);
+        }
+        int64_t lo = 0, hi = Pb;   // first k with target(order_ba[k]) >= i
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (chamfer_target(order_ba[mid], b_first, b_num, a_first, N, Pb, idx_ba) < i) lo = mid + 1;
+            else hi = mid;
+        }
+        for (int64_t k = lo; k < Pb; ++k) {
+            const int64_t j = order_ba[k];
+            if (chamfer_target(j, b_first, b_num, a_first, N, Pb, idx_ba) != i) break;
+            const double w = 2.0 * (double)gb[j];
+            s0 += w * (ax - (double)b[3 * j]); s1 += w * (ay - (double)b[3 * j + 1]); s2 += w * (az - (double)b[3 * j + 2]);
+        }
+    }
+    grad_a[3 * i] = (float)s0; grad_a[3 * i + 1] = (float)s1; grad_a[3 * i + 2] = (float)s2;
+}
+
+// one thread per point: threads [0, Px) write grad_x (when given), threads [Px, Px + Py) grad_y
+__global__ __launch_bounds__(256) void chamfer_backward_kernel(const float *__restrict__ x, const float *__restrict__ y,
+                                                               const int64_t *__restrict__ x_first, const int64_t *__restrict__ x_num, int64_t Px,
+                                                               const int64_t *__restrict__ y_first, const int64_t *__restrict__ y_num, int64_t Py,
+                                                               int N, const int64_t *__restrict__ idx_xy, const int64_t *__restrict__ idx_yx,
+                                                               const int64_t *__restrict__ order_xy, const int64_t *__restrict__ order_yx,
+                                                               const float *__restrict__ gx, const float *__restrict__ gy,
+                                                               float *__restrict__ grad_x, float *__restrict__ grad_y)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < Px) {
+        if (grad_x) chamfer_grad_point(t, x, y, x_first, x_num, y_first, y_num, N, Py, idx_xy, idx_yx, order_yx, gx, gy, grad_x);
+    } else if (t < Px + Py) {
+        if (grad_y) chamfer_grad_point(t - Px, y, x, y_first, y_num, x_first, x_num, N, Px, idx_yx, idx_xy, order_xy, gy, gx, grad_y);
+    }
+}
+
+}  // namespace dss
+
+extern "C" size_t dss_nearest_workspace(int N, int64_t Py) { return dss_knn_workspace(N, Py); }
+
+extern "C" int dss_nearest_points(const float *x, const int64_t *x_first, const int64_t *x_num, int64_t Px, const float *y,
+                                  const int64_t *y_first, const int64_t *y_num, int64_t Py, int N, float *d2, int64_t *idx,
+                                  void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "dss_nearest_points";
+    if (N <= 0 || Px < 0 || Py < 0) {
+        set_error("%s: bad sizes N=%d Px=%lld Py=%lld", who, N, (long long)Px, (long long)Py);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (Px == 0) return DSS_OK;
+    if (!x || !x_first || !x_num || !y_first || !y_num || !d2 || !idx || (Py > 0 && !y)) {
+        set_error("%s: NULL tensor pointer", who);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (!workspace || workspace_bytes < dss_nearest_workspace(N, Py)) {
+        set_error("%s: workspace too small", who);
+        return DSS_ERR_WORKSPACE;
+    }
+    // the target's grid, by the self query's build (the plan only matters to the queries above: none is launched)
+    const KnnCall c = {who, y, y_first, y_num, N, Py, 1, nullptr, nullptr, -1.0f, as_stream(stream), carve_knn(workspace, N, Py),
+                       plan_query(Py, 1, false)};
+    if (Py > 0)
+        if (int rc = build_grid(c, KnnView())) return rc;
+    // small inputs: one wavefront per workgroup, so that the wavefronts spread over all CUs (as plan_query does)
+    const unsigned block = Px <= 131072 ? 64u : 256u;
+    hipLaunchKernelGGL(nearest_query_kernel, dim3((unsigned)((Px + block - 1) / block)), dim3(block), 0, c.st, x, x_first, x_num, Px,
+                       y_first, y_num, N, c.w.grids, c.w.stride, c.w.offsets, c.w.sorted, d2, idx);
+    return check_launch(who);
+}
+
+extern "C" int dss_chamfer_backward(const float *x, const float *y, const int64_t *x_first, const int64_t *x_num, int64_t Px,
+                                    const int64_t *y_first, const int64_t *y_num, int64_t Py, int N, const int64_t *idx_xy,
+                                    const int64_t *idx_yx, const int64_t *order_xy, const int64_t *order_yx, const float *gx,
+                                    const float *gy, float *grad_x, float *grad_y, void *stream)
+{
+    const char *who = "dss_chamfer_backward";
+    if (N <= 0 || Px < 0 || Py < 0) {
+        set_error("%s: bad sizes N=%d Px=%lld Py=%lld", who, N, (long long)Px, (long long)Py);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (Px + Py == 0 || (!grad_x && !grad_y)) return DSS_OK;
+    if (!x_first || !x_num || !y_first || !y_num || (Px > 0 && (!x || !idx_xy || !gx)) || (Py > 0 && (!y || !idx_yx || !gy)) ||
+        (grad_x && Py > 0 && !order_yx) || (grad_y && Px > 0 && !order_xy)) {
+        set_error("%s: NULL tensor pointer", who);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    const int64_t blocks = (Px + Py + 255) / 256;
+    if (blocks > 0x7fffffffll) { set_error("%s: too many points", who); return DSS_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(chamfer_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, y, x_first, x_num, Px,
+                       y_first, y_num, Py, N, idx_xy, idx_yx, order_xy, order_yx, gx, gy, grad_x, grad_y);
+    return check_launch(who);
+}

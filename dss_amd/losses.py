@@ -195,3 +195,149 @@ def calc_dr_loss(rgba_pred, img, mask_img, lambda_dr_rgb: float = 1.0, lambda_dr
         mask_img = mask_img.float()
     total, rest = _ImageLoss.apply(rgba_pred, img, mask_img, float(lambda_dr_rgb), float(lambda_dr_silhouette))
     return {"loss": total, "loss_dr_rgb": rest[0], "loss_dr_silhouette": rest[1], "loss_iou": rest[2]}
+
+
+class _ChamferSide:
+    """One argument of `chamfer_distance` as packed clouds: ``src`` is the tensor autograd sees (padded (N,P,3), or the
+    packed (P,3) of a `PointClouds3D`), ``pack`` / ``unpack_grad`` move between it and the packed (P,3) the kernels take."""
+
+    def __init__(self, points, lengths, normals, name):
+        if hasattr(points, "points_packed"):
+            self.src = points.points_packed()
+            self.sizes = [int(p.shape[0]) for p in points.points_list()]   # host-side sizes: no device synchronisation
+            self.sel, self.padded_shape = None, None
+            normals = points.normals_packed()
+        elif torch.is_tensor(points):
+            if points.dim() != 3:
+                raise ValueError("Expected points to be of shape (N, P, D)")
+            if points.shape[2] != 3:
+                raise ValueError("dss_amd.losses.chamfer_distance is built for 3-D points, got D = %d" % points.shape[2])
+            N, P = points.shape[0], points.shape[1]
+            if lengths is not None and (lengths.dim() != 1 or lengths.shape[0] != N):
+                raise ValueError("Expected lengths to be of shape (N,)")
+            if normals is not None and (normals.dim() != 3 or normals.shape[:2] != points.shape[:2]):
+                raise ValueError("Expected normals to be of shape (N, P, 3")
+            self.src = points
+            self.sizes = [P] * N if lengths is None else [int(v) for v in lengths.tolist()]
+            if any(s > P for s in self.sizes):
+                raise ValueError("%s_lengths exceed the padded size %d" % (name, P))
+            self.padded_shape = tuple(points.shape)
+            self.sel = None
+            if any(s != P for s in self.sizes):   # flat positions of the valid entries of the padded tensor
+                self.sel = torch.cat([torch.arange(n * P, n * P + s, device=points.device) for n, s in enumerate(self.sizes)])
+        else:
+            raise ValueError("The input pointclouds should be either Pointclouds objects or torch.Tensor of shape (minibatch, "
+                             "num_points, 3).")
+        if len(self.sizes) == 0 or any(s <= 0 for s in self.sizes):
+            raise ValueError("chamfer_distance: %s has an empty cloud (sizes %s): its mean distance is undefined" % (name, self.sizes))
+        dev = self.src.device
+        self.num = torch.tensor(self.sizes, dtype=torch.int64, device=dev)
+        first, run = [], 0
+        for s in self.sizes:
+            first.append(run)
+            run += s
+        self.first = torch.tensor(first, dtype=torch.int64, device=dev)
+        self.P = run
+        self.normals = None if normals is None else self.pack(normals.detach())
+
+    def pack(self, t):
+        if self.padded_shape is None:
+            return t.contiguous()
+        flat = t.reshape(-1, t.shape[-1])
+        return flat.contiguous() if self.sel is None else flat.index_select(0, self.sel)
+
+    def unpack_grad(self, g):
+        if self.padded_shape is None:
+            return g
+        if self.sel is None:
+            return g.view(self.padded_shape)
+        return g.new_zeros((self.padded_shape[0] * self.padded_shape[1], 3)).index_copy_(0, self.sel, g).view(self.padded_shape)
+
+    def per_point(self, per_cloud):
+        return torch.repeat_interleave(per_cloud, self.num, output_size=self.P)
+
+    def cloud_sums(self, v):
+        """(P,) -> (N,) per-cloud sums in a fixed order (no atomics)."""
+        if all(s == self.sizes[0] for s in self.sizes):
+            return v.view(len(self.sizes), self.sizes[0]).sum(1)
+        return torch.stack([c.sum() for c in v.split(self.sizes)])
+
+
+def _normal_term(own, near):   # 1 - |cos|, F.cosine_similarity(dim = 1, eps = 1e-6)
+    return 1 - torch.abs(torch.nn.functional.cosine_similarity(own, near, dim=1, eps=1e-6))
+
+
+class _Chamfer(autograd.Function):
+    """Both nearest-point searches, the normal term and the reductions as ONE node; backward = dss_chamfer_backward."""
+
+    @staticmethod
+    def forward(ctx, x_src, y_src, sx, sy, weights, batch_reduction, point_reduction):
+        x, y = sx.pack(x_src.detach()), sy.pack(y_src.detach())
+        d2x, idx_xy = ops.nearest_points(x, sx.first, sx.num, y, sy.first, sy.num)
+        d2y, idx_yx = ops.nearest_points(y, sy.first, sy.num, x, sx.first, sx.num)
+        N = len(sx.sizes)
+        # d (result) / d (squared distance of a point of cloud n), per side: weight, point and batch reduction
+        kx = torch.ones(N, dtype=x.dtype, device=x.device) if weights is None else weights.to(x.dtype).reshape(N)
+        ky = kx
+        if point_reduction == "mean":
+            kx, ky = kx / sx.num, ky / sy.num
+        if batch_reduction == "mean":
+            div = weights.sum() if weights is not None else N
+            kx, ky = kx / div, ky / div
+        cx, cy = sx.per_point(kx), sy.per_point(ky)
+        cham = sx.cloud_sums(d2x * cx) + sy.cloud_sums(d2y * cy)
+        cham_normals = None
+        if sx.normals is not None and sy.normals is not None:
+            # the neighbours' normals: one row gather each (dss_gather_rows), rows = packed ids of the nearest points
+            near_x = ops.gather_rows(sy.normals, (idx_xy + sx.per_point(sy.first)).to(torch.int32), 1, sx.P, 3)[0]
+            near_y = ops.gather_rows(sx.normals, (idx_yx + sy.per_point(sx.first)).to(torch.int32), 1, sy.P, 3)[0]
+            cham_normals = sx.cloud_sums(_normal_term(sx.normals, near_x) * cx) + sy.cloud_sums(_normal_term(sy.normals, near_y) * cy)
+        if batch_reduction is not None:
+            cham = cham.sum()
+            cham_normals = None if cham_normals is None else cham_normals.sum()
+        ctx.save_for_backward(x, y, idx_xy, idx_yx, kx, ky)
+        ctx.sides = (sx, sy)
+        if cham_normals is not None:
+            ctx.mark_non_differentiable(cham_normals)
+        return cham, cham_normals
+
+    @staticmethod
+    def backward(ctx, grad_cham, _grad_normals):
+        x, y, idx_xy, idx_yx, kx, ky = ctx.saved_tensors
+        sx, sy = ctx.sides
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx, gy = sx.per_point(grad_cham * kx), sy.per_point(grad_cham * ky)   # grad_cham: () or (N,)
+        grad_x, grad_y = ops.chamfer_backward(x, sx.first, sx.num, y, sy.first, sy.num, idx_xy, idx_yx, gx, gy, want_x, want_y)
+        return (sx.unpack_grad(grad_x) if want_x else None, sy.unpack_grad(grad_y) if want_y else None, None, None, None, None, None)
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
+                     batch_reduction="mean", point_reduction: str = "mean"):
+    """``pytorch3d.loss.chamfer_distance`` -- the 3-D metric of `Trainer.evaluate_3d` (trainer.py:144-171,
+    ``chamfer_distance(target, model)`` -> ``chamfer_point``, ``chamfer_normal``) -- on the HIP path: both nearest-point
+    searches (``dss_nearest_points``), the gather of the neighbours' normals and the backward (``dss_chamfer_backward``).
+
+    ``x``, ``y``: padded float32 (N,P,3) tensors with optional ``*_lengths`` (N,) and ``*_normals`` (N,P,3), or
+    `dss_amd.cloud.PointClouds3D` (lengths and normals then come from the clouds).  ``weights`` (N,), ``batch_reduction`` in
+    ("mean", "sum", None), ``point_reduction`` in ("mean", "sum") as in pytorch3d.  Returns ``(cham_dist, cham_normals)``;
+    ``cham_normals`` = mean of 1 - |cos| between a point's normal and its nearest neighbour's (eps 1e-6), None unless both
+    sides have normals.  One autograd node: ``cham_dist`` is differentiable w.r.t. the points of x and y (index lists held
+    constant, deterministic), ``cham_normals`` carries no graph.  An empty cloud on either side raises ValueError."""
+    if batch_reduction is not None and batch_reduction not in ("mean", "sum"):
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError('point_reduction must be one of ["mean", "sum"]')
+    sx, sy = _ChamferSide(x, x_lengths, x_normals, "x"), _ChamferSide(y, y_lengths, y_normals, "y")
+    N = len(sx.sizes)
+    if len(sy.sizes) != N:
+        raise ValueError("y does not have the correct shape.")
+    if weights is not None:
+        if weights.size(0) != N:
+            raise ValueError("weights must be of shape (N,).")
+        if not (weights >= 0).all():
+            raise ValueError("weights cannot be negative.")
+        if weights.sum() == 0.0:   # pytorch3d: a zero that keeps the graph
+            per_cloud = torch.stack([c.sum() for c in sx.pack(sx.src).split(sx.sizes)]) * weights.reshape(N)
+            zero = (per_cloud.sum() if batch_reduction is not None else per_cloud) * 0.0
+            return zero, zero
+    return _Chamfer.apply(sx.src, sy.src, sx, sy, weights, batch_reduction, point_reduction)

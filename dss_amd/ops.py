@@ -1353,3 +1353,8 @@ def image_loss_band_backward_partials(rgba_band, target_rgb, target_mask, rows, 
                   float(lambda_rgb), float(lambda_silhouette), partials, grad_total, grad, losses, sums, rsn, rsh,
                   alpha_out, asn, ash)
     return (grad, losses, sums) if want_sums else (grad, losses)
+
+
+# The cross-cloud operators (nearest point in ANOTHER cloud, the chamfer backward on it) live in cross_cloud.py and go
+# through the same boundary (`_lib.call`); they are operators of this module like the ones above.
+from .cross_cloud import chamfer_backward, chamfer_order, nearest_points, packed_cloud_ids  # noqa: E402,F401

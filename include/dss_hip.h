@@ -540,6 +540,40 @@ DSS_API int dss_knn_kth_sqdist_view(const float *points, const int64_t *first_id
                                     size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest point in ANOTHER cloud, and the chamfer point term's gradient: the 3-D metric of the reference's loop,
+ * Trainer.evaluate_3d (DSS/training/trainer.py:144-171) = pytorch3d.loss.chamfer_distance(target, model) [third party,
+ * not vendored: interface and semantics as restated by compat/pytorch3d/loss/chamfer.py].
+ * dss_nearest_points: cloud n of x (packed, x_first / x_num) is searched in cloud n of y.  d2[i] = smallest squared
+ * distance from x point i to the points of its target cloud, in the difference form (dx dx + dy dy) + dz dz, dx = x - y,
+ * fp32; idx[i] = that point's cloud-local id in y, ties to the smaller id (the (distance, id) order of dss_knn_points).
+ * Exact: the grid of y is the self query's, the query is a ring walk from the clamped start cell that stops when the
+ * best distance is no larger than the distance from the query's real position to the unvisited region.  A query whose
+ * target cloud is empty, and a packed x slot owned by no cloud (its position is not read), get d2 = 0, idx = -1.
+ * Workspace: dss_nearest_workspace(N, Py) (= dss_knn_workspace(N, Py)).
+ * dss_chamfer_backward: with the index lists held constant (as in pytorch3d),
+ *   grad_x[i] = 2 gx[i] (x_i - y_nn(i)) + sum_{j: nn(j) = i} 2 gy[j] (x_i - y_j)        (and symmetrically grad_y)
+ * where gx (Px,) / gy (Py,) = d loss / d d2 of the two searches, idx_xy (Px,) / idx_yx (Py,) their cloud-local results.
+ * The many-to-one sum is deterministic and free of float atomics: order_xy (Px,) is the permutation of x's packed ids
+ * sorted by (packed id of the nearest point in y, own id) and order_yx (Py,) likewise for y; one thread per point finds
+ * its segment by binary search and adds it front to back in double, so a repeated call returns the same bits.  Pairs
+ * with idx < 0 contribute nothing (they sort behind every real target).  Both outputs are fully written; either
+ * gradient pointer may be NULL (then the order list only it needs -- order_yx for grad_x, order_xy for grad_y -- may
+ * be NULL as well).
+ * ------------------------------------------------------------------------------------------- */
+DSS_API size_t dss_nearest_workspace(int N, int64_t Py);
+DSS_API int dss_nearest_points(const float *x /* (Px,3) */, const int64_t *x_first, const int64_t *x_num, int64_t Px,
+                               const float *y /* (Py,3) */, const int64_t *y_first, const int64_t *y_num, int64_t Py, int N,
+                               float *d2 /* (Px,) */, int64_t *idx /* (Px,) cloud-local id in y */,
+                               void *workspace, size_t workspace_bytes, void *stream);
+DSS_API int dss_chamfer_backward(const float *x, const float *y,
+                                 const int64_t *x_first, const int64_t *x_num, int64_t Px,
+                                 const int64_t *y_first, const int64_t *y_num, int64_t Py, int N,
+                                 const int64_t *idx_xy /* (Px,) */, const int64_t *idx_yx /* (Py,) */,
+                                 const int64_t *order_xy /* (Px,) */, const int64_t *order_yx /* (Py,) */,
+                                 const float *gx /* (Px,) d loss / d d2_x */, const float *gy /* (Py,) */,
+                                 float *grad_x /* (Px,3) */, float *grad_y /* (Py,3) */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Phong shading of the points = LightingTexture.forward (DSS/core/texture.py:65-125):
  * apply_lighting (:26-63) with lighting.py:10-77 (diffuse) and :80-172 (specular) for L PointLights
  * (point_lights = 1: light_vec = location, direction = location - point, lighting.py:239-302) or
