@@ -34,3 +34,15 @@ def calling_thread_backward():
         yield
     finally:
         torch.autograd.set_multithreading_enabled(was)
+
+
+_CLOUD_OPS = ("upsample", "upsample_clouds", "remove_outliers")
+
+
+def __getattr__(name):
+    """``dss_amd.upsample`` / ``upsample_clouds`` / ``remove_outliers`` (dss_amd/cloud_ops.py), imported on first use so that
+    ``import dss_amd`` itself stays free of torch."""
+    if name in _CLOUD_OPS:
+        from . import cloud_ops
+        return getattr(cloud_ops, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

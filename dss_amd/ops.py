@@ -1358,3 +1358,5 @@ def image_loss_band_backward_partials(rgba_band, target_rgb, target_mask, rows, 
 # The cross-cloud operators (nearest point in ANOTHER cloud, the chamfer backward on it) live in cross_cloud.py and go
 # through the same boundary (`_lib.call`); they are operators of this module like the ones above.
 from .cross_cloud import chamfer_backward, chamfer_order, nearest_points, packed_cloud_ids  # noqa: E402,F401
+# likewise the two kernels of an upsampling round (upsample_ops.py; the rounds themselves are dss_amd.cloud_ops.upsample)
+from .upsample_ops import upsample_candidates, upsample_insert  # noqa: E402,F401

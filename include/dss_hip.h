@@ -574,6 +574,50 @@ DSS_API int dss_chamfer_backward(const float *x, const float *y,
                                  float *grad_x /* (Px,3) */, float *grad_y /* (Py,3) */, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One round of sparsity upsampling: `upsample` of DSS/core/cloud.py:555-632 inserts points where a neighbourhood is
+ * sparsest, a tenth of the cloud per round.  The reference materialises an (N,P,K,K,3) tensor; here one kernel searches the
+ * K x K candidates of every point and a second one assembles the grown cloud.  Between them the caller sorts `key` (one
+ * ascending integer sort per cloud, dss_amd/cloud_ops.py) and hands back the selected ids.
+ * The round, for cloud n of P_n points, neighbourhood size K, and n_new[n] in 0 .. P_n / 10 points to insert:
+ *   q_0 .. q_{K-1} = entries 1 .. K of p's dss_knn_points(K + 1) list (self dropped; the list's (distance, id) order)
+ *   mid_j = (q_j + 2 p) / 3             m_j = min_l |mid_j - q_l|^2 over l = 0 .. K-1 (l = j included), squared distances in
+ *                                        the form (dx dx + dy dy) + dz dz, fp32, every operation rounded on its own
+ *   s(p) = max_j m_j                    j*(p) = the SMALLEST j that attains it (the reference takes a norm first: the root
+ *                                        is monotone, so the order by the square is the same)
+ *   selection = the n_new[n] points with the largest s, ties to the SMALLER cloud-local id, emitted in ascending
+ *               (s, then descending id) order = the reverse of the selection order = the reference's "last n_new of an
+ *               ascending sort"
+ *   new cloud = [the selected candidates mid_{j*} in that order ; the old points in their order]      (cloud.py:620-625)
+ *   attributes (P,C), optional: old rows copied, a new row = (a[q_{j*}] + 2 a[p]) / 3, no renormalisation.
+ * dss_upsample_candidates: knn_idx (P, K + 1) int64 cloud-local.  Every packed slot of the three outputs is written;
+ * sparsity_sq[p] = s(p), father[p] = j*(p), key[p] = (float bits of sparsity_sq) << 32 | (0xffffffff - cloud-local id) --
+ * sparsity_sq >= 0, so its bit pattern orders like its value and ONE ascending integer sort of a cloud's keys gives the
+ * emission order (as int64 the keys are non-negative).  A slot that no cloud owns gets 0, 0, 0 and its position is not read;
+ * a cloud of fewer than K + 1 points uses the num_pts[n] - 1 neighbours it has (none: sparsity_sq = 0, father = 0).
+ * dss_upsample_insert: sel (n_sel,) int64 = the PACKED ids (into `points`) of the selected points, cloud after cloud, each
+ * cloud's n_new[n] in emission order, n_sel = sum n_new; old_first / old_num the ranges of the P old rows, new_first /
+ * new_num those of the P_out = P + n_sel grown rows, new_num[n] = old_num[n] + n_new[n].  One thread per output row, no
+ * atomics, a repeated call returns the same bits; rows of no cloud are written as zeros.  attrs / out_attrs come together
+ * or are both NULL, 1 <= C <= 16.
+ * Refusals (DSS_ERR_INVALID_ARGUMENT, nothing launched): K < 1 or K + 1 > 40 (the limit of dss_knn_points); C outside
+ * 1 .. 16; P_out != P + n_sel, which covers a target below the current size -- a round only grows.  The cloud sizes
+ * themselves are device arrays here, so the two refusals that need them (a target below the current size of ONE cloud, a
+ * cloud with a deficit and fewer than max(10, K + 1) points, on which the reference loops forever at P / 10 == 0) are made
+ * from the host integers of `dss_amd.cloud_ops.upsample`, as ValueError before any launch.  The kernels follow no id that
+ * leaves its cloud or the packed array.
+ * ------------------------------------------------------------------------------------------- */
+DSS_API int dss_upsample_candidates(const float *points /* (P,3) */, const int64_t *knn_idx /* (P,K+1) */,
+                                    const int64_t *first_idx, const int64_t *num_pts, int N, int64_t P, int K,
+                                    float *sparsity_sq /* (P,) */, int32_t *father /* (P,) j* */, uint64_t *key /* (P,) */,
+                                    void *stream);
+DSS_API int dss_upsample_insert(const float *points /* (P,3) */, const float *attrs /* (P,C) or NULL */, int C,
+                                const int64_t *knn_idx /* (P,K+1) */, const int32_t *father /* (P,) */,
+                                const int64_t *sel /* (n_sel,) */, const int64_t *old_first, const int64_t *old_num,
+                                const int64_t *new_first, const int64_t *new_num, const int64_t *n_new /* (N,) */, int N,
+                                int K, int64_t P, int64_t P_out, int64_t n_sel, float *out_points /* (P_out,3) */,
+                                float *out_attrs /* (P_out,C) or NULL */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Phong shading of the points = LightingTexture.forward (DSS/core/texture.py:65-125):
  * apply_lighting (:26-63) with lighting.py:10-77 (diffuse) and :80-172 (specular) for L PointLights
  * (point_lights = 1: light_vec = location, direction = location - point, lighting.py:239-302) or
