@@ -16,6 +16,7 @@ Differences that a caller can observe (documented in DESIGN.md / INTEGRATION.md)
   when ``raster_settings.backface_culling`` is on, where masking would change h and therefore the image);
 * a point exactly on a pixel centre contributes 0 to the occupancy gradient (reference: NaN).
 """
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -119,14 +120,18 @@ class PointsRasterizationSettings:
         self.antialiasing_sigma = antialiasing_sigma
 
 
+def _radii_clip(radii_backward_scaler, clip_pts_grad):
+    """``(radii_s, clip)`` as the backward operators take them; ``clip_pts_grad=None`` = no clip = -1"""
+    return float(radii_backward_scaler), -1.0 if clip_pts_grad is None else float(clip_pts_grad)
+
+
 def _raster_forward(ctx, pts_screen, ellipse_param, cutoff_threshold, radii, cloud_to_packed_first_idx,
                     num_points_per_cloud, depth_merging_threshold, image_size, points_per_pixel, bin_size,
                     max_points_per_bin, radii_backward_scaler, clip_pts_grad):
     idx, zbuf, qvalue_map, occ_map, visible = ops.splat_points(
         pts_screen, ellipse_param, cutoff_threshold, radii, cloud_to_packed_first_idx, num_points_per_cloud,
         depth_merging_threshold, image_size, points_per_pixel, bin_size, max_points_per_bin, return_visible=True)
-    ctx.radii_backward_scaler = radii_backward_scaler
-    ctx.clip_pts_grad = -1.0 if clip_pts_grad is None else float(clip_pts_grad)
+    ctx.radii_backward_scaler, ctx.clip_pts_grad = _radii_clip(radii_backward_scaler, clip_pts_grad)
     ctx.save_for_backward(pts_screen, radii, idx, visible, cloud_to_packed_first_idx, num_points_per_cloud)
     # unused output gradients arrive as None instead of dense zero tensors: an all-zero zbuf gradient (train_mvr.py:
     # zbuf feeds no loss) then costs neither an (N,S,S,K) allocation nor the scatter pass + separate clip launch
@@ -202,8 +207,8 @@ class _ProjectAndSetup(autograd.Function):
     and -- when they require grad -- the camera matrices M and V (`ops.camera_backward`)."""
 
     @staticmethod
-    def forward(ctx, world, normals, h, M, V, znear, zfar, first_idx, num_points, image_size, cutoff, sigma,
-                backface, shared, vr6=None, frame_normals=None):
+    def forward(ctx, world, normals, h, M, V, znear, zfar, first_idx, num_points, vr6, frame_normals, image_size, cutoff,
+                sigma, backface, shared):
         info = ops.point_setup(world, normals, h, M, V, znear, zfar, first_idx, num_points, image_size, cutoff,
                                sigma, backface, shared, vr6=vr6, frame_normals=frame_normals)
         ctx.save_for_backward(world, M, V, first_idx, num_points, info["valid"])
@@ -225,6 +230,23 @@ class _ProjectAndSetup(autograd.Function):
             # (g_screen arrives clipped from the rasterizer's backward: no clip here, like the projection above)
             gM, gV = ops.camera_backward(world, M, V, first_idx, num_points, g_screen, valid, ctx.shared)
         return (gw, None, None, gM, gV) + (None,) * 11
+
+
+class _Prepared(namedtuple("_Prepared", "world normals h M V znear zfar first_idx num_points vr6 frame_n N shared "
+                                        "out_clouds raster_settings")):
+    """What `SurfaceSplatting._prepare` makes of the (camera, cloud) objects of one call.  The first eleven fields are the
+    tensors the kernels read, in the order of `ops.FusedPlan.forward` without the features: every consumer takes the sequence
+    from here.  ``out_clouds`` and ``raster_settings`` belong to ONE call: the memo keeps the record without them."""
+    __slots__ = ()
+
+    def kernel_inputs(self, feats):   # (world, normals, h, M, V, znear, zfar, first_idx, num_points, feats, vr6, frame_n)
+        return self[:9] + (feats,) + self[9:11]
+
+    def setup_inputs(self):           # (the same without the features: what the per-point setup reads)
+        return self[:11]
+
+    def for_call(self, out_clouds, raster_settings):
+        return _Prepared(*self[:13], out_clouds, raster_settings)
 
 
 _CAMERA_FIELDS = ("R", "T", "znear", "zfar", "fov", "aspect_ratio")
@@ -252,6 +274,25 @@ def _kw_state(v):
         return ("v", float(v))
     except (TypeError, ValueError):
         return ("id", id(v))
+
+
+def _per_camera(cameras, kwargs, name, default, N: int, dev) -> torch.Tensor:
+    """float32 (N,) on ``dev`` of a per-camera value: the cameras' own field, else the call's keyword, else ``default``"""
+    t = getattr(cameras, name, kwargs.get(name, default))
+    if (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev and t.dim() == 1
+            and t.shape[0] == N and t.is_contiguous()):
+        return t  # the usual case: no copy, no launch
+    return torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1).expand(N).contiguous()
+
+
+def _per_point_h(d, sizes, copies: int = 1) -> torch.Tensor:
+    """h per point (rasterizer.py:383-388); a cloud shared by ``copies`` cameras: per (camera, point), packed like the extended cloud"""
+    h = (0.5 * d).clamp_(5e-5, 0.01).reshape(-1)
+    if min(sizes) < 7:   # "knn search is unreliable, set sq_dist manually" (rasterizer.py:378-379): 0.5 * 1e-3
+        small = torch.cat([torch.full((n,), n < 7, dtype=torch.bool) for n in sizes]).to(h.device)
+        small = small.repeat(copies) if copies > 1 else small
+        h = torch.where(small, torch.full_like(h, 0.5e-3), h)
+    return h
 
 
 def knn_variance_scale(point_clouds, K: int = 7) -> torch.Tensor:
@@ -286,7 +327,19 @@ class SurfaceSplatting(torch.nn.Module):
         # must take the reference's order to give the reference's image; the shipped configs (backface_culling: false)
         # keep the sync-free masked path.
         self.compact_culled = compact_culled
-        self._Vrk_h = None
+        # state of the render entry: last h, last culling flags, `_prepare`'s memo, the last _GraphedRender; a FusedPlan /
+        # RowShardedRender per problem shape; the default of the ``order_refresh`` keyword
+        self._Vrk_h = self._last_valid = self._prepare_memo = self._graphed = None
+        self._plans, self._sharded, self.order_refresh = {}, {}, 0
+
+    def _settings(self, kwargs):
+        return kwargs.get("raster_settings", self.raster_settings)
+
+    def _cameras(self, kwargs):
+        cameras = kwargs.get("cameras", self.cameras)
+        if cameras is None:
+            raise ValueError("Cameras must be specified either at initialization or in the forward pass")
+        return cameras
 
     def compacts(self, raster_settings=None) -> bool:
         """whether a forward with these settings takes the reference's drop-the-culled-points order"""
@@ -313,12 +366,10 @@ class SurfaceSplatting(torch.nn.Module):
         sizes = [p.shape[0] for p in point_clouds.points_list()]
         radius = self.frnn_radius if (self.frnn_radius is not None and self.frnn_radius > 0) else -1.0
         invariant, isotropic = bool(raster_settings.Vrk_invariant), bool(raster_settings.Vrk_isotropic)
-        if not invariant and not isotropic:
-            h = torch.zeros(n_total, device=point_clouds.device)   # unused: the anisotropic variance comes from _local_frames
-            self._Vrk_h = h
-            return h
-        pts = point_clouds.points_packed().detach()
-        if view is not None:
+        pts = point_clouds.points_packed().detach() if (invariant or isotropic) else None
+        if pts is None:   # (h is unused: the anisotropic variance comes from _local_frames)
+            h = torch.zeros(n_total, device=point_clouds.device)
+        elif view is not None:
             V, znear, zfar, shared = view
             N = V.shape[0]
             if not shared and N > 1 and len(sizes) == N and min(sizes) == max(sizes) and sizes[0] > 0 and self.detect_identical_clouds:
@@ -339,27 +390,14 @@ class SurfaceSplatting(torch.nn.Module):
                     f1, n1 = (first.new_zeros(N), num[:1].expand(N).contiguous()) if shared else (first, num)
                     h = ops.renderable_mean_clamp(d, pts, V, znear, zfar, f1, n1, shared, 0.5, 5e-5, 1e-3, 0.5e-3, 7)
                 else:
-                    # per point (rasterizer.py:383-388); for a shared cloud one value per (camera, point) pair, packed like
-                    # the extended cloud
-                    h = (0.5 * d).clamp_(5e-5, 0.01).reshape(-1)
-                    if min(sizes) < 7:   # "knn search is unreliable, set sq_dist manually" (rasterizer.py:378-379)
-                        small = torch.cat([torch.full((n,), n < 7, dtype=torch.bool) for n in sizes]).to(h.device)
-                        small = small.repeat(N) if (shared and N > 1) else small
-                        h = torch.where(small, torch.full_like(h, 0.5e-3), h)
-            self._Vrk_h = h
-            return h
-        with torch.no_grad():
-            # through dss_amd.neighbours: one search serves this statistic and the regularisers of the same iteration
-            d = neighbours.kth_sqdist(pts, first, num, sizes, 7, radius=radius)
-        if invariant:
-            # one scalar per cloud: mean_i(0.5 max kNN-7 d^2) clamped to [5e-5, 1e-3]; clouds with fewer than
-            # 7 points use sq_dist = 1e-3 (rasterizer.py:320-326)
-            h = ops.cloud_mean_clamp(d, first, num, 0.5, 5e-5, 1e-3, 0.5e-3, 7)
+                    h = _per_point_h(d, sizes, N if shared else 1)
         else:
-            h = (0.5 * d).clamp_(5e-5, 0.01)  # per point (rasterizer.py:383-388)
-            if min(sizes) < 7:  # "knn search is unreliable, set sq_dist manually" (rasterizer.py:378-379): 0.5 * 1e-3
-                small = torch.cat([torch.full((n,), n < 7, dtype=torch.bool) for n in sizes]).to(h.device)
-                h = torch.where(small, torch.full_like(h, 0.5e-3), h)
+            with torch.no_grad():
+                # through dss_amd.neighbours: one search serves this statistic and the regularisers of the same iteration
+                d = neighbours.kth_sqdist(pts, first, num, sizes, 7, radius=radius)
+                # invariant: one scalar per cloud, mean_i(0.5 max kNN-7 d^2) clamped to [5e-5, 1e-3]; clouds with fewer than
+                # 7 points use sq_dist = 1e-3 (rasterizer.py:320-326)
+                h = ops.cloud_mean_clamp(d, first, num, 0.5, 5e-5, 1e-3, 0.5e-3, 7) if invariant else _per_point_h(d, sizes)
         self._Vrk_h = h
         return h
 
@@ -380,6 +418,29 @@ class SurfaceSplatting(torch.nn.Module):
                               scaler=torch.zeros((batch_size, S, S, K), device=device),
                               occupancy=torch.zeros((batch_size, S, S), device=device))
 
+    @staticmethod
+    def _memo_key(point_clouds, cameras, raster_settings, kwargs):
+        """(key of `_prepare`'s memo, the objects it names by id: kept alive with it, so no id is recycled), or None"""
+        h_given = kwargs.get("Vrk_h", None)
+        pl, nl = point_clouds.points_list(), point_clouds.normals_list()
+        cam_state = tuple(getattr(cameras, k, None) for k in _CAMERA_FIELDS)
+        # (only when the packed geometry IS the caller's tensor -- one cloud, or one tensor extended to the cameras: a
+        # concatenation of several tensors is a copy that has to be rebuilt from their current values)
+        if h_given is None or not (raster_settings.Vrk_invariant or raster_settings.Vrk_isotropic) or len(pl) < 1 or nl is None \
+                or not all(t is pl[0] for t in pl) or not all(t is nl[0] for t in nl) or _camera_needs_grad(cam_state):
+            return None
+        znear, zfar = kwargs.get("znear", None), kwargs.get("zfar", None)
+        key = (id(cameras), tuple(id(t) for t in cam_state), tuple(getattr(t, "_version", 0) for t in cam_state),
+               tuple(id(t) for t in pl), tuple(id(t) for t in nl), tuple(t.shape[0] for t in pl), id(h_given),
+               h_given._version, id(raster_settings), _kw_state(znear), _kw_state(zfar))
+        return key, (cameras, cam_state, pl, nl, h_given, raster_settings, znear, zfar)
+
+    @staticmethod
+    def _memo_may_keep(a, keep) -> bool:
+        """whether the record may be stored: only when the packed tensors ARE the caller's tensors (a duck-typed cloud whose
+        points_packed() is a copy -- pytorch3d's torch.cat -- would be served a stale copy after an in-place optimiser step)"""
+        return a.world is keep[2][0] and a.normals is keep[3][0] and not (a.M.requires_grad or a.V.requires_grad)
+
     def _prepare(self, point_clouds, **kwargs):
         """Everything the kernels need from the (camera, cloud) objects: packed world points / normals,
         variance scale, camera matrices, cloud ranges.  One cloud is shared by all N cameras
@@ -390,33 +451,13 @@ class SurfaceSplatting(torch.nn.Module):
         identities (+ the cameras' version counters); a caller-supplied ``Vrk_h`` then makes the call free of launches.
         Cameras that are being differentiated (a field requires grad, grad mode on) are never memoised: their matrices
         carry the autograd graph of ONE iteration."""
-        raster_settings = kwargs.get("raster_settings", self.raster_settings)
-        cameras = kwargs.get("cameras", self.cameras)
-        if cameras is None:
-            raise ValueError("Cameras must be specified either at initialization or in the forward pass")
-        self.cameras = cameras
-        h_given = kwargs.get("Vrk_h", None)
-        memo_key = None
-        pl, nl = point_clouds.points_list(), point_clouds.normals_list()
-        cam_state = tuple(getattr(cameras, k, None) for k in ("R", "T", "znear", "zfar", "fov", "aspect_ratio"))
-        # (only when the packed geometry IS the caller's tensor -- one cloud, or one tensor extended to the cameras: a
-        # concatenation of several tensors is a copy that has to be rebuilt from their current values)
-        if h_given is not None and (raster_settings.Vrk_invariant or raster_settings.Vrk_isotropic) and len(pl) >= 1 \
-                and all(t is pl[0] for t in pl) and nl is not None and all(t is nl[0] for t in nl) \
-                and not _camera_needs_grad(cam_state):
-            memo_key = (id(cameras), tuple(id(t) for t in cam_state), tuple(getattr(t, "_version", 0) for t in cam_state),
-                        tuple(id(t) for t in pl), None if nl is None else tuple(id(t) for t in nl),
-                        tuple(t.shape[0] for t in pl), id(h_given), h_given._version, id(raster_settings),
-                        _kw_state(kwargs.get("znear", None)), _kw_state(kwargs.get("zfar", None)))
-            hit = getattr(self, "_prepare_memo", None)
-            if hit is not None and hit[0] == memo_key:
-                a = dict(hit[1])
-                N = a["N"]
-                a["out_clouds"] = point_clouds if (not a["shared"] or len(point_clouds) == N) else point_clouds.extend(N)
-                a["raster_settings"] = raster_settings
-                return a
-        N = cameras.R.shape[0]
-        dev = point_clouds.device
+        raster_settings = self._settings(kwargs)
+        cameras = self.cameras = self._cameras(kwargs)
+        memo = self._memo_key(point_clouds, cameras, raster_settings, kwargs)
+        if memo is not None and self._prepare_memo is not None and self._prepare_memo[0] == memo[0]:
+            a = self._prepare_memo[1]
+            return a.for_call(point_clouds if (not a.shared or len(point_clouds) == a.N) else point_clouds.extend(a.N), raster_settings)
+        N, dev = cameras.R.shape[0], point_clouds.device
         shared = len(point_clouds) == 1 and N >= 1
         if not shared and len(point_clouds) != N:
             raise ValueError("need 1 or %d point clouds for %d cameras, got %d" % (N, N, len(point_clouds)))
@@ -424,23 +465,13 @@ class SurfaceSplatting(torch.nn.Module):
         # position / normal tensors, only the colours differ per camera: keep one copy of the geometry (shared-cloud
         # kernels, one kNN instead of N) and the per-camera colours
         geometry = point_clouds
-        if not shared and N > 1:
+        if not shared and N > 1 and isinstance(point_clouds, PointClouds3D):
             pl, nl = point_clouds.points_list(), point_clouds.normals_list()
             if all(t is pl[0] for t in pl) and nl is not None and all(t is nl[0] for t in nl):
-                shared = True
-                geometry = type(point_clouds)([pl[0]], [nl[0]]) if isinstance(point_clouds, PointClouds3D) else None
-                if geometry is None:
-                    shared, geometry = False, point_clouds
+                shared, geometry = True, type(point_clouds)([pl[0]], [nl[0]])
         M = cameras.get_full_projection_transform().get_matrix().to(dev, torch.float32).contiguous()
         V = cameras.get_world_to_view_transform().get_matrix().to(dev, torch.float32).contiguous()
-
-        def as_n(v, d):
-            t = getattr(cameras, v, kwargs.get(v, d))
-            if (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev and t.dim() == 1
-                    and t.shape[0] == N and t.is_contiguous()):
-                return t  # the usual case: no copy, no launch
-            return torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1).expand(N).contiguous()
-        znear, zfar = as_n("znear", 1.0), as_n("zfar", 100.0)
+        znear, zfar = _per_camera(cameras, kwargs, "znear", 1.0, N, dev), _per_camera(cameras, kwargs, "zfar", 100.0, N, dev)
         h = kwargs.get("Vrk_h", None)
         if h is None:
             h = self._variance_scale(geometry, raster_settings, kwargs.get("refresh", True), view=(V, znear, zfar, shared))
@@ -449,23 +480,15 @@ class SurfaceSplatting(torch.nn.Module):
             vr6, frame_n = self._local_frames(geometry)
         world, normals = geometry.points_packed(), geometry.normals_packed()
         if shared:
-            Pc = world.shape[0]
-            first_idx, num_points = shared_cloud_ranges(N, Pc, dev)  # cached: constant across iterations
+            first_idx, num_points = shared_cloud_ranges(N, world.shape[0], dev)  # cached: constant across iterations
             if h.numel() == 1:
                 h = h.reshape(1).expand(N).contiguous()
-            out_clouds = point_clouds if len(point_clouds) == N else point_clouds.extend(N)
         else:
             first_idx, num_points = point_clouds.cloud_to_packed_first_idx(), point_clouds.num_points_per_cloud()
-            out_clouds = point_clouds
-        a = dict(N=N, shared=shared, world=world, normals=normals, h=h.to(dev, torch.float32), M=M, V=V,
-                 znear=znear, zfar=zfar, first_idx=first_idx, num_points=num_points,
-                 out_clouds=out_clouds, raster_settings=raster_settings, vr6=vr6, frame_n=frame_n)
-        if memo_key is not None and world is pl[0] and normals is nl[0] and not (M.requires_grad or V.requires_grad):
-            # (only when the packed tensors ARE the caller's tensors: a duck-typed cloud whose points_packed() is a copy --
-            # pytorch3d's torch.cat -- would otherwise be served a stale copy after an in-place optimiser step)
-            # (the memo keeps the keyed objects alive -- an id cannot be recycled while it is the current entry)
-            keep = (cameras, cam_state, pl, nl, h_given, raster_settings, kwargs.get("znear", None), kwargs.get("zfar", None))
-            self._prepare_memo = (memo_key, {k: v for k, v in a.items() if k not in ("out_clouds", "raster_settings")}, keep)
+        a = _Prepared(world, normals, h.to(dev, torch.float32), M, V, znear, zfar, first_idx, num_points, vr6, frame_n,
+                      N, shared, point_clouds if (not shared or len(point_clouds) == N) else point_clouds.extend(N), raster_settings)
+        if memo is not None and self._memo_may_keep(a, memo[1]):
+            self._prepare_memo = (memo[0], a.for_call(None, None), memo[1])
         return a
 
     @staticmethod
@@ -506,19 +529,11 @@ class SurfaceSplatting(torch.nn.Module):
         scale h on those, rasterize them.  ``fragments.idx`` then labels the filtered packed cloud that is returned, integer
         for integer like the reference.  Costs boolean indexing with host syncs per call, which the default (masked)
         path avoids; results for every consumer of the (fragments, point_clouds) pair are the same either way."""
-        raster_settings = kwargs.get("raster_settings", self.raster_settings)
-        cameras = kwargs.get("cameras", self.cameras)
-        if cameras is None:
-            raise ValueError("Cameras must be specified either at initialization or in the forward pass")
-        N = cameras.R.shape[0]
-        dev = point_clouds.device
+        raster_settings, cameras = self._settings(kwargs), self._cameras(kwargs)
+        N, dev = cameras.R.shape[0], point_clouds.device
         pc = point_clouds if len(point_clouds) == N else point_clouds.extend(N)
         V = cameras.get_world_to_view_transform().get_matrix().to(dev, torch.float32)
-
-        def per_cam(name, default):
-            t = getattr(cameras, name, kwargs.get(name, default))
-            return torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1).expand(N)
-        znear, zfar = per_cam("znear", 1.0), per_cam("zfar", 100.0)
+        znear, zfar = _per_camera(cameras, kwargs, "znear", 1.0, N, dev), _per_camera(cameras, kwargs, "zfar", 100.0, N, dev)
         pl, nl, fl = pc.points_list(), pc.normals_list(), pc.features_list()
         keeps, pts_f, nrm_f, feat_f = [], [], [], []
         for n in range(N):
@@ -555,32 +570,24 @@ class SurfaceSplatting(torch.nn.Module):
         return fragments, filtered
 
     def forward(self, point_clouds, point_clouds_filter=None, **kwargs):
-        raster_settings = kwargs.get("raster_settings", self.raster_settings)
+        raster_settings = self._settings(kwargs)
         original_clouds = point_clouds
         if not point_clouds.isempty():
             point_clouds = self._apply_activation_filter(point_clouds, point_clouds_filter)
         if point_clouds.isempty():
-            cameras = kwargs.get("cameras", self.cameras)
-            return self._empty_fragments(cameras.R.shape[0], point_clouds.device, raster_settings), point_clouds
+            return self._empty_fragments(self._cameras(kwargs).R.shape[0], point_clouds.device, raster_settings), point_clouds
         if self.compacts(raster_settings):
             return self._forward_compacted(point_clouds, original_clouds, point_clouds_filter, **kwargs)
         return self._forward_masked(point_clouds, original_clouds, point_clouds_filter, **kwargs)
 
     def _forward_masked(self, point_clouds, original_clouds, point_clouds_filter, **kwargs):
-        raster_settings = kwargs.get("raster_settings", self.raster_settings)
         a = self._prepare(point_clouds, **kwargs)
-        N, shared, first_idx, num_points = a["N"], a["shared"], a["first_idx"], a["num_points"]
-
+        st, N, shared, first_idx, num_points = a.raster_settings, a.N, a.shared, a.first_idx, a.num_points
         pts_screen, ellipse, radii, scaler, cutoff, valid = _ProjectAndSetup.apply(
-            a["world"], a["normals"], a["h"], a["M"], a["V"], a["znear"], a["zfar"], first_idx, num_points,
-            raster_settings.image_size, raster_settings.cutoff_threshold, raster_settings.antialiasing_sigma,
-            bool(raster_settings.backface_culling), shared, a["vr6"], a["frame_n"])
-
+            *a.setup_inputs(), st.image_size, st.cutoff_threshold, st.antialiasing_sigma, bool(st.backface_culling), shared)
         idx, zbuf, qvalue_map, occ_map, visible = _EllipticalRasterizerWithVisibility.apply(
-            pts_screen, ellipse, cutoff, radii, first_idx, num_points, raster_settings.depth_merging_threshold,
-            raster_settings.image_size, raster_settings.points_per_pixel, raster_settings.bin_size,
-            raster_settings.max_points_per_bin, raster_settings.radii_backward_scaler,
-            raster_settings.clip_pts_grad)
+            pts_screen, ellipse, cutoff, radii, first_idx, num_points, st.depth_merging_threshold, st.image_size,
+            st.points_per_pixel, st.bin_size, st.max_points_per_bin, st.radii_backward_scaler, st.clip_pts_grad)
 
         # the per-fragment scaler gather of rasterizer.py:631-633 is fused into the blend kernel: the fragments keep
         # the per-POINT scaler (`scaler_packed`) and materialise the (N,H,W,K) `scaler` only if it is read
@@ -590,48 +597,59 @@ class SurfaceSplatting(torch.nn.Module):
         self._store_visibility(point_clouds_filter, visible, N, shared, original_clouds)
         if kwargs.get("verbose", False):
             info = {"radii": radii, "ellipse_params": ellipse, "cutoff_threshold": cutoff, "scaler": scaler}
-            return fragments, a["out_clouds"], info
-        return fragments, a["out_clouds"]
+            return fragments, a.out_clouds, info
+        return fragments, a.out_clouds
 
     def _lean_plan(self, a, feats, st):
         """The ops.FusedPlan of this call's shape, or None when the inputs need the general (checking, converting) path."""
         from .ops import FusedPlan
-        tensors = (a["world"], a["normals"], a["h"], a["M"], a["V"], a["znear"], a["zfar"], feats)
-        if not all(FusedPlan.lean_input(t) for t in tensors) or st.points_per_pixel > 32 or \
-                not FusedPlan.lean_input(a["first_idx"], torch.int64) or not FusedPlan.lean_input(a["num_points"], torch.int64) or \
-                (a["vr6"] is not None and not (FusedPlan.lean_input(a["vr6"]) and FusedPlan.lean_input(a["frame_n"]))):
+        world, normals, h, M, V, znear, zfar, first_idx, num_points, feats, vr6, frame_n = inputs = a.kernel_inputs(feats)
+        lean = FusedPlan.lean_input
+        if st.points_per_pixel > 32 or not all(lean(t) for t in inputs[:7] + (feats,)) \
+                or not (lean(first_idx, torch.int64) and lean(num_points, torch.int64)) \
+                or (vr6 is not None and not (lean(vr6) and lean(frame_n))):
             return None
-        dev, N, Pw = a["world"].device, a["N"], a["world"].shape[0]
-        if a["normals"].shape != a["world"].shape or tuple(a["M"].shape) != (N, 4, 4) or tuple(a["V"].shape) != (N, 4, 4) or \
-                a["znear"].numel() != N or a["zfar"].numel() != N or a["first_idx"].numel() != N:
+        dev, N, Pw = world.device, a.N, world.shape[0]
+        if normals.shape != world.shape or tuple(M.shape) != (N, 4, 4) or tuple(V.shape) != (N, 4, 4) or \
+                znear.numel() != N or zfar.numel() != N or first_idx.numel() != N:
             return None
-        P = N * Pw if a["shared"] else Pw
+        P = N * Pw if a.shared else Pw
         if feats.shape[0] != P or P == 0:
             return None
         try:
-            per_point = ops._h_mode(a["h"], N, Pw, P, a["shared"])
+            per_point = ops._h_mode(h, N, Pw, P, a.shared)
         except RuntimeError:   # (the general path raises it again, as the caller's error)
             return None
-        key = (dev, N, Pw, P, int(st.image_size), int(st.points_per_pixel), feats.shape[1], bool(a["shared"]), per_point,
-               a["vr6"] is not None, bool(st.backface_culling), float(st.cutoff_threshold), float(st.antialiasing_sigma),
+        key = (dev, N, Pw, P, int(st.image_size), int(st.points_per_pixel), feats.shape[1], bool(a.shared), per_point,
+               vr6 is not None, bool(st.backface_culling), float(st.cutoff_threshold), float(st.antialiasing_sigma),
                float(st.depth_merging_threshold))
-        plans = self.__dict__.setdefault("_plans", {})
-        plan = plans.get(key)
+        plan = self._plans.get(key)
         if plan is None:
-            if len(plans) > 8:
-                plans.clear()
-            plan = plans[key] = FusedPlan(*key)
+            if len(self._plans) > 8:
+                self._plans.clear()
+            plan = self._plans[key] = FusedPlan(*key)
         return plan
 
-    def _render_sharded(self, a, feats, st, part, point_clouds_filter, original_clouds, **kwargs):
-        """`render_fused` on a row partition (`dss_amd.sharded.RowShardedRender`, multi-GPU): -> (image, fragments, clouds)
-        with ``image`` the FULL (N,S,S,C+1) render (gathered from all ranks) or, with ``band_only=True``, this rank's rows
-        (N,rows,S,C+1) for `dss_amd.distributed.band_image_loss`.  The fragments are those of the rank's rows."""
+    @staticmethod
+    def _arena_fragments(plan, arena, a, want_fragments, want_visible):
+        """(fragments, visible) of a lean plan's arena, each None unless wanted: only what somebody reads becomes tensor objects"""
+        if not (want_fragments or want_visible):
+            return None, None
+        view = lambda name: plan.view(arena, name)
+        visible = view("visible").view(torch.bool)
+        return PointFragments(idx=view("idx"), zbuf=view("zbuf"), qvalue=view("qvalue"), scaler=view("scaler"),
+                              occupancy=view("occupancy"), geometry=(view("pts_screen"), view("radii"), visible, a.first_idx,
+                                                                     a.num_points)) if want_fragments else None, visible
+
+    # -- the routes of render_fused: each -> (image, fragments or None, visible or None) ---------------------------------
+    def _render_sharded(self, a, feats, st, part, scalars, order_refresh, kwargs):
+        """On a row partition (`dss_amd.sharded.RowShardedRender`, multi-GPU): the FULL (N,S,S,C+1) image gathered from all ranks
+        or, with ``band_only=True``, this rank's rows (N,rows,S,C+1) for `distributed.band_image_loss`; this rank's fragments."""
         from .sharded import RowShardedRender
         if st.points_per_pixel > 32:
             raise ValueError("a row-partitioned render needs points_per_pixel <= 32 (the fused kernels)")
-        dev, N, Pw = a["world"].device, a["N"], a["world"].shape[0]
-        P = N * Pw if a["shared"] else Pw
+        dev, N, Pw = a.world.device, a.N, a.world.shape[0]
+        P = N * Pw if a.shared else Pw
         S, K, C = int(st.image_size), int(st.points_per_pixel), int(feats.shape[1])
         if part.cyclic and C != 3:
             # the tile-row-cyclic variants of the backward are built for RGB features (include/dss_hip.h)
@@ -647,31 +665,68 @@ class SurfaceSplatting(torch.nn.Module):
         if gradient == "auto":   # (a replicated loss hands the owner form the full gradient: no alpha-plane exchange)
             gradient = choose_gradient_exchange(N, Pw, P, S, C, part.world_size, band_loss=band_only)
         group = kwargs.get("process_group", None)
-        key = (dev, N, Pw, P, S, K, C, bool(a["shared"]), bool(st.backface_culling), float(st.cutoff_threshold),
+        key = (dev, N, Pw, P, S, K, C, bool(a.shared), bool(st.backface_culling), float(st.cutoff_threshold),
                float(st.antialiasing_sigma), float(st.depth_merging_threshold), part.world_size, part.rank, part.cyclic,
                None if part.cyclic else tuple(part._bounds), gradient, id(group))
-        engines = self.__dict__.setdefault("_sharded", {})
-        engine = engines.get(key)
+        engine = self._sharded.get(key)
         if engine is None:
-            if len(engines) > 4:
-                engines.clear()
-            engine = engines[key] = RowShardedRender(part, N, Pw, P, S, K, C, dev, a["shared"], st.cutoff_threshold,
-                                                     st.antialiasing_sigma, st.depth_merging_threshold,
-                                                     bool(st.backface_culling), group=group, gradient=gradient,
-                                                     static_buffers=False)
-        aux = (a["normals"], a["h"], a["M"], a["V"], a["znear"], a["zfar"], a["first_idx"], a["num_points"], a["vr6"],
-               a["frame_n"], float(st.radii_backward_scaler), -1.0 if st.clip_pts_grad is None else float(st.clip_pts_grad),
-               band_only, int(kwargs.get("order_refresh", getattr(self, "order_refresh", 0)) or 0))
-        image = _RenderRowSharded.apply(a["world"], feats.contiguous(), engine, aux)
-        f = engine.f
-        visible = engine.vis_all.view(torch.bool)
-        fragments = None
+            if len(self._sharded) > 4:
+                self._sharded.clear()
+            engine = self._sharded[key] = RowShardedRender(
+                part, N, Pw, P, S, K, C, dev, a.shared, st.cutoff_threshold, st.antialiasing_sigma, st.depth_merging_threshold,
+                bool(st.backface_culling), group=group, gradient=gradient, static_buffers=False)
+        image = _RenderRowSharded.apply(a.world, feats.contiguous(), engine, (a,) + scalars + (band_only, order_refresh))
+        f, visible, fragments = engine.f, engine.vis_all.view(torch.bool), None
         if kwargs.get("want_fragments", True):
-            fragments = PointFragments(idx=f["idx"], zbuf=f["zbuf"], qvalue=f["qvalue"], scaler=f["scaler"],
-                                       occupancy=f["occupancy"],
-                                       geometry=(f["pts_screen"], f["radii"], visible, a["first_idx"], a["num_points"]))
-        self._store_visibility(point_clouds_filter, visible.clone(), a["N"], a["shared"], original_clouds)
-        return image, fragments, a["out_clouds"]
+            fragments = PointFragments(idx=f["idx"], zbuf=f["zbuf"], qvalue=f["qvalue"], scaler=f["scaler"], occupancy=f["occupancy"],
+                                       geometry=(f["pts_screen"], f["radii"], visible, a.first_idx, a.num_points))
+        return image, fragments, visible.clone()   # (the engine's flags are overwritten by its next forward)
+
+    def _render_graphed(self, a, feats, st, plan, scalars, want, point_clouds, h_given):
+        """`_GraphedRender`: two hipGraphs over static buffers, captured again when an address, the plan or a scalar changed"""
+        inputs, (radii_s, clip) = a.kernel_inputs(feats), scalars
+        G = self._graphed
+        if G is None or G.plan is not plan or G.ptrs != _GraphedRender.signature(inputs) or G.radii_s != radii_s or G.clip != clip:
+            G = self._graphed = _GraphedRender(plan, inputs, radii_s, clip, a.shared)
+        # key of the steady-state shortcut (`_replays`): only for one un-extended cloud whose tensors ARE the graph's inputs
+        pl, nl, fl, cams = point_clouds.points_list(), point_clouds.normals_list(), point_clouds.features_list(), self.cameras
+        G.call_key = None
+        if len(pl) == 1 and a.N == 1 and h_given is not None and nl is not None and fl is not None \
+                and pl[0] is a.world and fl[0] is feats and hasattr(cams, "R") and hasattr(cams, "T"):
+            G.call_key = (pl[0], nl[0], fl[0], h_given, cams, st, h_given._version, _camera_state(cams),
+                          tuple(getattr(st, n, None) for n in PointsRasterizationSettings.__slots__))   # (settings mutate in place)
+        image = _RenderFusedGraphed.apply(a.world, feats, G)
+        return (image,) + self._arena_fragments(plan, G.arena, a, *want)
+
+    def _render_lean(self, a, feats, plan, scalars, want):
+        """`_RenderFusedLean`: the plan's prebuilt calls, M and V stay out of the autograd graph."""
+        image, arena = _RenderFusedLean.apply(a.world, feats, plan, (a,) + scalars)
+        return (image,) + self._arena_fragments(plan, arena, a, *want)
+
+    def _render_general(self, a, feats, st, order_refresh):
+        """`_RenderFused`: the checking, converting operators; the only route that differentiates the cameras."""
+        image, idx, zbuf, qv, occ, scaler, pts_screen, radii, visible = _RenderFused.apply(
+            *a.kernel_inputs(feats.contiguous()), st.image_size, st.points_per_pixel, st.cutoff_threshold,
+            st.depth_merging_threshold, st.antialiasing_sigma, bool(st.backface_culling), a.shared, st.radii_backward_scaler,
+            st.clip_pts_grad, order_refresh)
+        return image, PointFragments(idx=idx, zbuf=zbuf, qvalue=qv, scaler=scaler, occupancy=occ,
+                                     geometry=(pts_screen, radii, visible, a.first_idx, a.num_points)), visible
+
+    def _replays(self, point_clouds, kwargs) -> bool:
+        """whether a graphed call is the SAME call as the last one (same tensor objects, cameras, settings, h: the steady state
+        of a training loop): nothing to prepare, nothing to check but the two addresses an optimiser could have replaced"""
+        G = self._graphed
+        if G is None or G.call_key is None:
+            return False
+        pl, nl, fl = point_clouds.points_list(), point_clouds.normals_list(), point_clouds.features_list()
+        k = G.call_key
+        return len(pl) == 1 and pl[0] is k[0] and nl is not None and nl[0] is k[1] and fl is not None and fl[0] is k[2] \
+            and kwargs.get("Vrk_h", None) is k[3] and kwargs.get("cameras", self.cameras) is k[4] \
+            and kwargs.get("raster_settings", self.raster_settings) is k[5] and k[3]._version == k[6] \
+            and pl[0].data_ptr() == G.ptrs[0][0] and fl[0].data_ptr() == G.ptrs[9][0] \
+            and all(getattr(k[4], n, None) is t and getattr(t, "_version", 0) == v for n, t, v in k[7]) \
+            and not _camera_needs_grad(t for _n, t, _v in k[7]) \
+            and k[8] == tuple(getattr(k[5], n, None) for n in PointsRasterizationSettings.__slots__)
 
     def render_fused(self, point_clouds, point_clouds_filter=None, **kwargs):
         """Rasterize AND blend in the fused kernels (``dss_render_forward`` / ``dss_render_backward``):
@@ -681,97 +736,49 @@ class SurfaceSplatting(torch.nn.Module):
         ``T``, ``fov``, ... (a loss on ``fragments.zbuf`` needs the unfused path).  Differentiable cameras take the general
         node (`_RenderFused`: separate projection backward + `ops.camera_backward`); ``graphed=True`` and
         ``row_partition=...`` do not carry camera gradients and raise NotImplementedError rather than drop them."""
+        graphed, want_fragments = kwargs.get("graphed", False), kwargs.get("want_fragments", True)
+        # 1. the steady state of a graphed training loop: replay
+        if graphed and point_clouds_filter is None and not want_fragments and self._replays(point_clouds, kwargs):
+            return _RenderFusedGraphed.apply(point_clouds.points_list()[0], point_clouds.features_list()[0], self._graphed), None, point_clouds
+        # 2. the activation filter; an empty cloud gives empty fragments and a zero image, like forward()
         original_clouds = point_clouds
-        if kwargs.get("graphed", False) and point_clouds_filter is None and not kwargs.get("want_fragments", True):
-            # graphed replay of the SAME call as last time (same tensor objects, cameras, settings, h: the steady state of
-            # a training loop): nothing to prepare, nothing to check but the two addresses an optimiser could have replaced
-            G = self.__dict__.get("_graphed")
-            if G is not None and G.call_key is not None:
-                pl, nl, fl = point_clouds.points_list(), point_clouds.normals_list(), point_clouds.features_list()
-                k = G.call_key
-                if len(pl) == 1 and pl[0] is k[0] and nl is not None and nl[0] is k[1] and fl is not None and fl[0] is k[2] \
-                        and kwargs.get("Vrk_h", None) is k[3] and kwargs.get("cameras", self.cameras) is k[4] \
-                        and kwargs.get("raster_settings", self.raster_settings) is k[5] and k[3]._version == k[6] \
-                        and pl[0].data_ptr() == G.ptrs[0][0] and fl[0].data_ptr() == G.ptrs[9][0] \
-                        and all(getattr(k[4], n, None) is t and getattr(t, "_version", 0) == v for n, t, v in k[7]) \
-                        and not _camera_needs_grad(t for _n, t, _v in k[7]) \
-                        and k[8] == tuple(getattr(k[5], n, None) for n in PointsRasterizationSettings.__slots__):
-                    return _RenderFusedGraphed.apply(pl[0], fl[0], G), None, point_clouds
         if not point_clouds.isempty():
             point_clouds = self._apply_activation_filter(point_clouds, point_clouds_filter)
-        if point_clouds.isempty():  # like forward(): empty fragments, zero image
-            st = kwargs.get("raster_settings", self.raster_settings)
-            cameras = kwargs.get("cameras", self.cameras)
-            frag = self._empty_fragments(cameras.R.shape[0], point_clouds.device, st)
-            image = torch.zeros(tuple(frag.occupancy.shape) + (4,), device=point_clouds.device)
-            return image, frag, point_clouds
+        if point_clouds.isempty():
+            frag = self._empty_fragments(self._cameras(kwargs).R.shape[0], point_clouds.device, self._settings(kwargs))
+            return torch.zeros(tuple(frag.occupancy.shape) + (4,), device=point_clouds.device), frag, point_clouds
+        # 3. the kernels' inputs
         a = self._prepare(point_clouds, **kwargs)
-        st = a["raster_settings"]
-        feats = a["out_clouds"].features_packed()
+        st, feats = a.raster_settings, a.out_clouds.features_packed()
+        # 4. what no route renders
         if feats.shape[1] > 8:
             raise ValueError("render_fused blends at most 8 feature channels, got %d (use the unfused forward() + "
                              "renderer for wider features)" % feats.shape[1])
         part = kwargs.get("row_partition", None)
-        cam_grad = _camera_needs_grad((a["M"], a["V"]))
-        if cam_grad and (part is not None or kwargs.get("graphed", False)):
+        cam_grad = _camera_needs_grad((a.M, a.V))
+        if cam_grad and (part is not None or graphed):
             raise NotImplementedError(
                 "%s does not carry gradients to the cameras (a camera tensor requires grad): render without it, or detach "
                 "the cameras" % ("row_partition=..." if part is not None else "graphed=True"))
+        # 5. the route; the lean node keeps M and V out of the graph  (order_refresh: include/dss_hip.h DSS_WS_ORDER_*)
+        order_refresh = int(kwargs.get("order_refresh", self.order_refresh) or 0)
+        scalars = _radii_clip(st.radii_backward_scaler, st.clip_pts_grad)
+        plan = None if (cam_grad or part is not None) else self._lean_plan(a, feats, st)
         if part is not None:
-            return self._render_sharded(a, feats, st, part, point_clouds_filter, original_clouds, **kwargs)
-        lean = None if cam_grad else self._lean_plan(a, feats, st)   # (the lean node keeps M and V out of the graph)
-        # renderer-owned cached point order (large clouds; include/dss_hip.h DSS_WS_ORDER_*): refreshed every k-th call
-        order_refresh = int(kwargs.get("order_refresh", getattr(self, "order_refresh", 0)) or 0)
-        if lean is not None:
-            lean.order_refresh = order_refresh
-        if lean is not None and kwargs.get("graphed", False):
-            inputs = (a["world"], a["normals"], a["h"], a["M"], a["V"], a["znear"], a["zfar"], a["first_idx"], a["num_points"],
-                      feats, a["vr6"], a["frame_n"])
-            radii_s = float(st.radii_backward_scaler)
-            clip = -1.0 if st.clip_pts_grad is None else float(st.clip_pts_grad)
-            G = self.__dict__.get("_graphed")
-            if G is None or G.plan is not lean or G.ptrs != _GraphedRender.signature(inputs) or G.radii_s != radii_s \
-                    or G.clip != clip:
-                G = self._graphed = _GraphedRender(lean, inputs, radii_s, clip, a["shared"])
-            # key of the steady-state shortcut at the top: only for one un-extended cloud whose tensors ARE the graph's inputs
-            pl, nl, fl = point_clouds.points_list(), point_clouds.normals_list(), point_clouds.features_list()
-            h_given, cams = kwargs.get("Vrk_h", None), kwargs.get("cameras", self.cameras)
-            G.call_key = None
-            if len(pl) == 1 and a["N"] == 1 and h_given is not None and nl is not None and fl is not None \
-                    and pl[0] is a["world"] and fl[0] is feats and hasattr(cams, "R") and hasattr(cams, "T"):
-                G.call_key = (pl[0], nl[0], fl[0], h_given, cams, st, h_given._version,
-                              _camera_state(cams),
-                              tuple(getattr(st, n, None) for n in PointsRasterizationSettings.__slots__))   # (settings mutate in place)
-            image = _RenderFusedGraphed.apply(a["world"], feats, G)
-            arena = G.arena
-        elif lean is not None:
-            aux = (a["normals"], a["h"], a["M"], a["V"], a["znear"], a["zfar"], a["first_idx"], a["num_points"], a["vr6"],
-                   a["frame_n"], float(st.radii_backward_scaler), -1.0 if st.clip_pts_grad is None else float(st.clip_pts_grad),
-                   a["shared"])
-            image, arena = _RenderFusedLean.apply(a["world"], feats, lean, aux)
-        if lean is not None:
-            want = kwargs.get("want_fragments", True)
-            fragments = None
-            if want or (point_clouds_filter is not None and hasattr(point_clouds_filter, "set_filter")):
-                visible = lean.view(arena, "visible").view(torch.bool)
-                if want:
-                    fragments = PointFragments(idx=lean.view(arena, "idx"), zbuf=lean.view(arena, "zbuf"),
-                                               qvalue=lean.view(arena, "qvalue"), scaler=lean.view(arena, "scaler"),
-                                               occupancy=lean.view(arena, "occupancy"),
-                                               geometry=(lean.view(arena, "pts_screen"), lean.view(arena, "radii"), visible,
-                                                         a["first_idx"], a["num_points"]))
-                self._store_visibility(point_clouds_filter, visible, a["N"], a["shared"], original_clouds)
-            return image, fragments, a["out_clouds"]
-        outs = _RenderFused.apply(a["world"], feats.contiguous(), a["normals"], a["h"],
-                                  a["M"], a["V"], a["znear"], a["zfar"], a["first_idx"], a["num_points"],
-                                  st.image_size, st.points_per_pixel, st.cutoff_threshold, st.depth_merging_threshold,
-                                  st.antialiasing_sigma, bool(st.backface_culling), a["shared"],
-                                  st.radii_backward_scaler, st.clip_pts_grad, a["vr6"], a["frame_n"], order_refresh)
-        image, idx, zbuf, qv, occ, scaler, pts_screen, radii, visible = outs
-        fragments = PointFragments(idx=idx, zbuf=zbuf, qvalue=qv, scaler=scaler, occupancy=occ,
-                                   geometry=(pts_screen, radii, visible, a["first_idx"], a["num_points"]))
-        self._store_visibility(point_clouds_filter, visible, a["N"], a["shared"], original_clouds)
-        return image, fragments, a["out_clouds"]
+            image, fragments, visible = self._render_sharded(a, feats, st, part, scalars, order_refresh, kwargs)
+        elif plan is None:
+            image, fragments, visible = self._render_general(a, feats, st, order_refresh)
+        else:
+            plan.order_refresh = order_refresh
+            want = (want_fragments, point_clouds_filter is not None and hasattr(point_clouds_filter, "set_filter"))
+            if graphed:
+                image, fragments, visible = self._render_graphed(a, feats, st, plan, scalars, want, point_clouds, kwargs.get("Vrk_h", None))
+            else:
+                image, fragments, visible = self._render_lean(a, feats, plan, scalars, want)
+        # 6. the visibility goes back into the filter object
+        if visible is not None:
+            self._store_visibility(point_clouds_filter, visible, a.N, a.shared, original_clouds)
+        return image, fragments, a.out_clouds
 
 
 class _RenderRowSharded(autograd.Function):
@@ -781,13 +788,13 @@ class _RenderRowSharded(autograd.Function):
 
     @staticmethod
     def forward(ctx, world, features, engine, aux):
-        normals, h, M, V, znear, zfar, first, num, vr6, frame_n, radii_s, clip, band_only, order_refresh = aux
-        f = engine.forward(world, normals, h, M, V, znear, zfar, first, num, features, vr6, frame_n, order_refresh)
+        a, radii_s, clip, band_only, order_refresh = aux
+        f = engine.forward(*a.kernel_inputs(features), order_refresh)
         # (private copies of what lives in the engine's exchange buffers: a second render before this one's backward --
         # Model.prune_points, an evaluation pass -- must not change what this node differentiates)
         vis = engine.start_exchange().clone()
         ctx.save_for_backward(world)
-        ctx.engine, ctx.f, ctx.vis, ctx.aux = engine, f, vis, (M, V, first, num, radii_s, clip, not band_only)
+        ctx.engine, ctx.f, ctx.vis, ctx.aux = engine, f, vis, (a.M, a.V, a.first_idx, a.num_points, radii_s, clip, not band_only)
         # band_only: the image all-gather stays in flight behind the loss and the backward (`engine.full_image()` waits for
         # it; the next forward does before it overwrites the send buffer)
         image = engine.band_image if band_only else engine.full_image()
@@ -876,10 +883,10 @@ class _RenderFusedLean(autograd.Function):
 
     @staticmethod
     def forward(ctx, world, features, plan, aux):
-        normals, h, M, V, znear, zfar, first, num, vr6, frame_n, radii_s, clip, shared = aux
-        arena = plan.forward(world, normals, h, M, V, znear, zfar, first, num, features, vr6, frame_n)
+        a, radii_s, clip = aux
+        arena = plan.forward(*a.kernel_inputs(features))
         ctx.save_for_backward(world)
-        ctx.plan, ctx.arena, ctx.aux = plan, arena, (M, V, first, num, radii_s, clip, shared)
+        ctx.plan, ctx.arena, ctx.aux = plan, arena, (a.M, a.V, a.first_idx, a.num_points, radii_s, clip, a.shared)
         image = plan.image(arena)
         ctx.mark_non_differentiable(arena)
         return image, arena
@@ -903,16 +910,14 @@ class _RenderFused(autograd.Function):
     backward = dss_render_backward (+clip) -> dss_project_backward, and dss_camera_backward when M / V require grad."""
 
     @staticmethod
-    def forward(ctx, world, features, normals, h, M, V, znear, zfar, first_idx, num_points, image_size,
-                points_per_pixel, cutoff, merge_thr, sigma, backface, shared, radii_s, clip, vr6=None,
-                frame_normals=None, order_refresh=0):
+    def forward(ctx, world, normals, h, M, V, znear, zfar, first_idx, num_points, features, vr6, frame_normals,
+                image_size, points_per_pixel, cutoff, merge_thr, sigma, backface, shared, radii_s, clip, order_refresh=0):
         f = ops.render_forward(world, normals, h, M, V, znear, zfar, first_idx, num_points, features, image_size,
                                points_per_pixel, cutoff, merge_thr, sigma, backface, shared, vr6=vr6,
                                frame_normals=frame_normals, order_refresh=int(order_refresh))
         ctx.save_for_backward(world, M, V, first_idx, num_points, f["idx"], f["qvalue"], f["wsum"], f["scaler"],
                               f["pts_screen"], f["radii"], f["visible"], f["valid"])
-        ctx.shared, ctx.radii_s = shared, float(radii_s)
-        ctx.clip = -1.0 if clip is None else float(clip)
+        ctx.shared, (ctx.radii_s, ctx.clip) = shared, _radii_clip(radii_s, clip)
         outs = (f["image"], f["idx"], f["zbuf"], f["qvalue"], f["occupancy"], f["scaler"], f["pts_screen"],
                 f["radii"], f["visible"])
         ctx.mark_non_differentiable(*outs[1:])
@@ -924,7 +929,7 @@ class _RenderFused(autograd.Function):
         # (larger renders take the 64-bit gather and the separate projection kernel instead of failing inside autograd)
         N, S, _, K = idx.shape
         # differentiable cameras: their reduction needs the SCREEN-space gradient, so the projection stays a launch of its own
-        need_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        need_cam = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
         fuse = not need_cam and ops.fuse_projection(N, S, K, g_image.shape[-1] - 1, ctx.shared, world.shape[0],
                                                     pts_screen.shape[0])
         g_feat, g_pts = ops.render_backward(g_image.contiguous(), idx, qv, wsum, scaler, pts_screen, radii, visible,
@@ -937,4 +942,4 @@ class _RenderFused(autograd.Function):
         if need_cam:
             # (the gather has applied the clip to g_pts: neither projection call clips again)
             g_M, g_V = ops.camera_backward(world, M, V, first_idx, num_points, g_pts, valid, ctx.shared)
-        return (g_world, g_feat, None, None, g_M, g_V) + (None,) * 16
+        return (g_world, None, None, g_M, g_V, None, None, None, None, g_feat) + (None,) * 12

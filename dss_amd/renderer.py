@@ -131,6 +131,18 @@ class SurfaceSplattingRenderer(torch.nn.Module):
             raise ValueError("row_partition is for %d image rows, the raster settings say %d" % (rp.S, S))
         return rp if rp.world_size > 1 else None
 
+    def _render_fused(self, point_clouds, kwargs, **route):
+        """the rasterizer's `render_fused` with the call's keywords + ``route`` -> RGBA, with ``verbose`` (RGBA, fragments)"""
+        verbose = kwargs.get("verbose", False)
+        kw = {k: v for k, v in kwargs.items() if k != "fragments"}
+        kw.update(route, want_fragments=bool(verbose))   # (only then are the fragment tensors materialised)
+        if self.order_refresh > 0 and "order_refresh" not in kw:
+            kw["order_refresh"] = self.order_refresh
+        images, fragments, _ = self.rasterizer.render_fused(point_clouds, **kw)
+        if images.shape[-1] != 4:  # RGBA contract of renderer.py:75-78: first three feature channels + occupancy
+            images = torch.cat([images[..., :3], images[..., -1:]], dim=-1)
+        return (images, fragments) if verbose else images
+
     def forward(self, point_clouds, **kwargs):
         if point_clouds.isempty():
             return None
@@ -144,32 +156,15 @@ class SurfaceSplattingRenderer(torch.nn.Module):
                     and not self.rasterizer.compacts(kwargs.get("raster_settings"))):
                 raise RuntimeError("a row-partitioned render needs dss_amd's SurfaceSplatting, a NormWeightedCompositor and "
                                    "the masked culling path (backface_culling off or compact_culled=False)")
-            kw = {k: v for k, v in kwargs.items() if k != "fragments"}
-            kw.update(row_partition=part, row_partition_auto=isinstance(self.row_partition, str) and self.row_partition == "auto",
-                      gradient_exchange=self.gradient_exchange, process_group=self.process_group,
-                      band_only=kwargs.get("band_only", self.row_output == "band"),
-                      want_fragments=bool(kwargs.get("verbose", False)))
-            if self.order_refresh > 0 and "order_refresh" not in kw:
-                kw["order_refresh"] = self.order_refresh
-            images, fragments, point_clouds = self.rasterizer.render_fused(point_clouds, **kw)
-            if images.shape[-1] != 4:
-                images = torch.cat([images[..., :3], images[..., -1:]], dim=-1)
-            return (images, fragments) if kwargs.get("verbose", False) else images
+            return self._render_fused(point_clouds, kwargs, row_partition=part, row_partition_auto=self.row_partition == "auto",
+                                      gradient_exchange=self.gradient_exchange, process_group=self.process_group,
+                                      band_only=kwargs.get("band_only", self.row_output == "band"))
         if (fragments is None and fused and hasattr(self.rasterizer, "render_fused")
                 and not self.rasterizer.compacts(kwargs.get("raster_settings"))   # (that mode rebuilds the clouds first: unfused)
                 and self._is_norm_weighted()
                 and (point_clouds.features_packed() is None or point_clouds.features_packed().shape[1] <= 8)  # render_fused: C <= 8
                 and self.rasterizer.raster_settings.points_per_pixel <= 32):
-            kw = {k: v for k, v in kwargs.items() if k != "fragments"}
-            kw["want_fragments"] = bool(kwargs.get("verbose", False))   # (only then are the fragment tensors materialised)
-            if self.graphed:
-                kw["graphed"] = True
-            if self.order_refresh > 0 and "order_refresh" not in kw:
-                kw["order_refresh"] = self.order_refresh
-            images, fragments, point_clouds = self.rasterizer.render_fused(point_clouds, **kw)
-            if images.shape[-1] != 4:  # RGBA contract of renderer.py:75-78: first three feature channels + occupancy
-                images = torch.cat([images[..., :3], images[..., -1:]], dim=-1)
-            return (images, fragments) if kwargs.get("verbose", False) else images
+            return self._render_fused(point_clouds, kwargs, **({"graphed": True} if self.graphed else {}))
         if fragments is None:
             if kwargs.get("verbose", False):
                 fragments, point_clouds, _ = self.rasterizer(point_clouds, **kwargs)
