@@ -149,17 +149,20 @@ __global__ __launch_bounds__(RB_BLOCK) void camera_partial_kernel(
     block_sum_store<16>(acc, partials + ((size_t)n * gridDim.x + blockIdx.x) * 16);
 }
 
-// (restated from shading.hip, whose kernels are left as they are: the same expressions under the same compiler flags)
+// (restated from shading.hip: the same expressions under the same compiler flags, the fp64 Jacobian included, so that the
+// camera centre and the lights see the pair's values that the points see)
 __device__ __forceinline__ float cam_safe_norm(float x, float y, float z) { return fmaxf(sqrtf(x * x + y * y + z * z), 1e-6f); }
 __device__ __forceinline__ void cam_normalize_backward(const float u[3], const float g[3], float out[3])
 {
-    const float raw = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    const float raw = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);  // the clamp decision is safe_norm's, in fp32
     if (raw > 1e-6f) {
-        const float inv = 1.0f / raw;
-        const float h[3] = {u[0] * inv, u[1] * inv, u[2] * inv};
-        const float dot = h[0] * g[0] + h[1] * g[1] + h[2] * g[2];
+        // in fp64 from the fp32 inputs, rounded once: shading.hip's normalize_backward, expression for expression
+        const double ud[3] = {(double)u[0], (double)u[1], (double)u[2]};
+        const double inv = 1.0 / sqrt(ud[0] * ud[0] + ud[1] * ud[1] + ud[2] * ud[2]);
+        const double h[3] = {ud[0] * inv, ud[1] * inv, ud[2] * inv};
+        const double dot = h[0] * (double)g[0] + h[1] * (double)g[1] + h[2] * (double)g[2];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) out[i] = (g[i] - h[i] * dot) * inv;
+        for (int i = 0; i < 3; ++i) out[i] = (float)(((double)g[i] - h[i] * dot) * inv);
     } else {
 #pragma unroll
         for (int i = 0; i < 3; ++i) out[i] = g[i] * 1e6f;  // clamped denominator: a constant scale

@@ -976,7 +976,9 @@ def _phong_common(world, normals, rgb, first, num, shared_cloud, ambient, diffus
 def phong_forward(world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, ambient, diffuse_color,
                   specular_color, light_vec, point_lights: bool, cam_center, shininess: float = 64.0,
                   shared_cloud: bool = False):
-    """Phong shading of the points (LightingTexture.forward, texture.py:65-125; lighting.py:10-172) -> (P,3)."""
+    """Phong shading of the points (LightingTexture.forward, texture.py:65-125; lighting.py:10-172) -> (P,3).
+    Per-camera clouds: the row of a packed point that no cloud owns is zeros.  A shared cloud with ``num[n] < Pw`` (which
+    `shared_cloud_ranges` never produces) leaves the rows of that camera's missing pairs unspecified."""
     dev, N, Pw, P, L, lead = _phong_common(
         world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
         specular_color, light_vec, point_lights, cam_center, shininess)
@@ -989,7 +991,9 @@ def phong_forward(world, normals, rgb, cloud_to_packed_first_idx, num_points_per
 def phong_backward(grad_out, world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, ambient,
                    diffuse_color, specular_color, light_vec, point_lights: bool, cam_center, shininess: float = 64.0,
                    shared_cloud: bool = False):
-    """-> (grad_world (Pw,3), grad_normals (Pw,3), grad_rgb (P,3))."""
+    """-> (grad_world (Pw,3), grad_normals (Pw,3), grad_rgb (P,3)).  Per-camera clouds: a packed point that no cloud owns
+    gets zeros in all three.  A shared cloud with ``num[n] < Pw`` (which `shared_cloud_ranges` never produces) leaves the
+    rows of ``grad_rgb`` of that camera's missing pairs unspecified; the other two sum the cameras that own the point."""
     dev, N, Pw, P, L, lead = _phong_common(
         world, normals, rgb, cloud_to_packed_first_idx, num_points_per_cloud, shared_cloud, ambient, diffuse_color,
         specular_color, light_vec, point_lights, cam_center, shininess, grad_out, "phong_backward")

@@ -630,6 +630,11 @@ DSS_API int dss_upsample_insert(const float *points /* (P,3) */, const float *at
  *   cam_center (N,3) = cameras.get_camera_center().
  * Backward: grad_world / grad_normals (Pw,3) (summed over the cameras of a shared cloud in camera order) and
  * grad_rgb (P,3); any of the three may be NULL.  This is the path by which an RGB loss reaches the normals.
+ * Rows that no cloud owns: with per-camera clouds (shared_cloud = 0, P = Pw) a packed point outside every
+ * [first_idx[n], first_idx[n] + num_pts[n]) gets exact zeros in its row of out, grad_world, grad_normals and grad_rgb.
+ * With a shared cloud, a camera with num_pts[n] < Pw leaves the rows of out / grad_rgb of its missing pairs
+ * UNSPECIFIED (first_idx is free, so the arguments do not say which rows those are; grad_world / grad_normals sum the
+ * cameras that do own the point, zeros when none does).
  * ------------------------------------------------------------------------------------------- */
 DSS_API int dss_phong_forward(const float *world, const float *normals, const float *rgb,
                               const int64_t *first_idx, const int64_t *num_pts, int N, int64_t Pw,

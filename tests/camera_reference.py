@@ -98,10 +98,11 @@ def phong(world, normals, rgb, first, num, ambient, kd, ks, lvec, point_lights, 
     return torch.cat(out, 0)
 
 
-def phong_backward_camera(grad_out, world, normals, first, num, ks, lvec, point_lights, cam, shininess, shared):
+def phong_backward_camera(grad_out, world, normals, first, num, ks, lvec, point_lights, cam, shininess, shared, dtype=F64):
     """closed form -> (grad_cam (N,3), abs_cam (N,3)) fp64: per pair gv = sum_l ga0_l r_l with
-    ga0 = (g . ks) s alpha^(s-1) on lit, facing fragments; gw = (gv - v^ (v^ . gv)) / |w|, w = camera - x"""
-    world, normals, g, ks, lvec, cam = (t.to(F64) for t in (world, normals, grad_out, ks, lvec, cam))
+    ga0 = (g . ks) s alpha^(s-1) on lit, facing fragments; gw = (gv - v^ (v^ . gv)) / |w|, w = camera - x
+    (`dtype=torch.float32`: the same formula in plain fp32 torch, to see what the number format alone costs)"""
+    world, normals, g, ks, lvec, cam = (t.to(dtype) for t in (world, normals, grad_out, ks, lvec, cam))
     N = cam.shape[0]
     gc, ac = torch.zeros(N, 3, dtype=F64), torch.zeros(N, 3, dtype=F64)
     for n, (lo, hi) in enumerate(_ranges(first, num)):
@@ -122,7 +123,7 @@ def phong_backward_camera(grad_out, world, normals, first, num, ks, lvec, point_
             ga0 = torch.where(on, gs * shininess * a0.clamp_min(0) ** (shininess - 1.0), torch.zeros_like(a0))
             gv = gv + ga0 * r
         gw = torch.where(wn > 1e-6, (gv - v * (v * gv).sum(1, keepdim=True)) / wn.clamp_min(1e-6), gv * 1e6)
-        gc[n], ac[n] = gw.sum(0), gw.abs().sum(0)
+        gc[n], ac[n] = gw.sum(0).to(F64), gw.to(F64).abs().sum(0)
     return gc, ac
 
 
