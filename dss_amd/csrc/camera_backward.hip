@@ -11,7 +11,8 @@
 //                                  grad_M[n][:, 3] = sum_p x (-(gx ndc_x + gy ndc_y) / w)       grad_M[n][:, 2] = 0
 //                                  grad_V[n][:, 2] = sum_p x gz              (the other columns of grad_V are 0)
 //   dss_phong_backward_camera  grad_cam[n] = + sum_p gw(n, p), gw = the gradient of w = camera - x that phong_kernel<true>
-//                              (shading.hip) subtracts from the point's gradient.
+//                              (shading.hip) subtracts from the point's gradient; the pair's arithmetic is phong.h's for
+//                              that kernel and the two Phong kernels here alike.
 //   dss_phong_backward_lights  the same shading differentiated w.r.t. the LIGHTS, which the reference keeps on the tape
 //                              (DSS/core/texture.py:25-63, :118-122; DSS/core/lighting.py:10-77, :80-172, :175-302):
 //                                  grad_ambient[n]     = sum_p g c            grad_diffuse[n][l]   = sum_p g c D_l
@@ -24,7 +25,7 @@
 // workspace, and a second small launch that adds the partials of every row (a camera, or a (camera, light)) in index order
 // in fp64 and writes fp32.  The launch boundary is the hand-off between the two stages: no flags, no fences, no counters
 // to re-initialise.
-#include "common.h"
+#include "phong.h"
 
 namespace dss {
 
@@ -149,41 +150,11 @@ __global__ __launch_bounds__(RB_BLOCK) void camera_partial_kernel(
     block_sum_store<16>(acc, partials + ((size_t)n * gridDim.x + blockIdx.x) * 16);
 }
 
-// (restated from shading.hip: the same expressions under the same compiler flags, the fp64 Jacobian included, so that the
-// camera centre and the lights see the pair's values that the points see)
-__device__ __forceinline__ float cam_safe_norm(float x, float y, float z) { return fmaxf(sqrtf(x * x + y * y + z * z), 1e-6f); }
-__device__ __forceinline__ void cam_normalize_backward(const float u[3], const float g[3], float out[3])
-{
-    const float raw = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);  // the clamp decision is safe_norm's, in fp32
-    if (raw > 1e-6f) {
-        // in fp64 from the fp32 inputs, rounded once: shading.hip's normalize_backward, expression for expression
-        const double ud[3] = {(double)u[0], (double)u[1], (double)u[2]};
-        const double inv = 1.0 / sqrt(ud[0] * ud[0] + ud[1] * ud[1] + ud[2] * ud[2]);
-        const double h[3] = {ud[0] * inv, ud[1] * inv, ud[2] * inv};
-        const double dot = h[0] * (double)g[0] + h[1] * (double)g[1] + h[2] * (double)g[2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) out[i] = (float)(((double)g[i] - h[i] * dot) * inv);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) out[i] = g[i] * 1e6f;  // clamped denominator: a constant scale
-    }
-}
-
-struct PhongCamArgs {
-    const float *grad_out, *world, *normals;  // (P,3), (Pw,3), (Pw,3)
-    const int64_t *first_idx, *num_pts;
-    int shared, L, point_lights;
-    int64_t Pw, P;
-    const float *ks, *lvec, *cam;             // (N,L,3), (N,L,3), (N,3)
-    float shininess;
-};
-
 // Stage 1 of dss_phong_backward_camera: one (camera, point) pair per lane and sweep.  The pair's gv (d loss / d v^) and
-// gw = normalize_backward(w, gv) are RESTATED from phong_kernel<true> (shading.hip) operation by operation -- sharing a
-// device function would have meant touching that kernel, whose generated code is pinned -- keeping only the terms gv
-// depends on (the specular chain; the diffuse colour and the point's rgb do not reach it).
-__global__ __launch_bounds__(RB_BLOCK) void phong_camera_partial_kernel(const PhongCamArgs A, int sweeps,
-                                                                        float *__restrict__ partials)
+// gw = normalize_backward(w, gv) are those of phong_kernel<true> (shading.hip) through phong.h, keeping only the terms
+// gv depends on (the specular chain; the diffuse colour and the point's rgb do not reach it).
+__global__ __launch_bounds__(RB_BLOCK) void phong_camera_partial_kernel(const PhongArgs A, const float *__restrict__ grad_out,
+                                                                        int sweeps, float *__restrict__ partials)
 {
     const int n = blockIdx.y;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -196,32 +167,22 @@ __global__ __launch_bounds__(RB_BLOCK) void phong_camera_partial_kernel(const Ph
         if (wi >= A.Pw) continue;
         const float x[3] = {A.world[3 * wi], A.world[3 * wi + 1], A.world[3 * wi + 2]};
         const float m[3] = {A.normals[3 * wi], A.normals[3 * wi + 1], A.normals[3 * wi + 2]};
-        const float mn = cam_safe_norm(m[0], m[1], m[2]);
-        const float nh[3] = {m[0] / mn, m[1] / mn, m[2] / mn};
-        const float g[3] = {A.grad_out[3 * p], A.grad_out[3 * p + 1], A.grad_out[3 * p + 2]};
+        const float g[3] = {grad_out[3 * p], grad_out[3 * p + 1], grad_out[3 * p + 2]};
         const float w[3] = {A.cam[3 * n] - x[0], A.cam[3 * n + 1] - x[1], A.cam[3 * n + 2] - x[2]};
-        const float wn = cam_safe_norm(w[0], w[1], w[2]);
-        const float v[3] = {w[0] / wn, w[1] / wn, w[2] / wn};
+        float nh[3], v[3];
+        unit(m, nh);
+        unit(w, v);
         float gv[3] = {0.f, 0.f, 0.f};
         for (int l = 0; l < A.L; ++l) {
-            const float *lv = A.lvec + ((size_t)n * A.L + l) * 3;
             const float *ks = A.ks + ((size_t)n * A.L + l) * 3;
-            float u[3] = {lv[0], lv[1], lv[2]};
-            if (A.point_lights) { u[0] -= x[0]; u[1] -= x[1]; u[2] -= x[2]; }
-            const float un = cam_safe_norm(u[0], u[1], u[2]);
-            const float d[3] = {u[0] / un, u[1] / un, u[2] / un};
-            const float ca = nh[0] * d[0] + nh[1] * d[1] + nh[2] * d[2];
-            const float r[3] = {-d[0] + 2.0f * (ca * nh[0]), -d[1] + 2.0f * (ca * nh[1]), -d[2] + 2.0f * (ca * nh[2])};
-            const float a0 = v[0] * r[0] + v[1] * r[1] + v[2] * r[2];
-            const bool lit = ca > 0.0f;
-            const float alpha = lit ? fmaxf(a0, 0.0f) : 0.0f;
+            const PhongLight t = phong_light(A, n, l, x, nh, v);
             const float gs = g[0] * ks[0] + g[1] * ks[1] + g[2] * ks[2];                        // d loss / d S
-            const float ga0 = (lit && a0 > 0.0f) ? gs * A.shininess * powf(alpha, A.shininess - 1.0f) : 0.0f;
+            const float ga0 = phong_ga0(t, gs, A.shininess);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) gv[i] += ga0 * r[i];
+            for (int i = 0; i < 3; ++i) gv[i] += ga0 * t.r[i];
         }
         float gw[3];
-        cam_normalize_backward(w, gv, gw);                      // w = camera - x
+        normalize_backward(w, gv, gw);                          // w = camera - x
 #pragma unroll
         for (int i = 0; i < 3; ++i) acc[i] += gw[i];
     }
@@ -232,27 +193,17 @@ __global__ __launch_bounds__(RB_BLOCK) void phong_camera_partial_kernel(const Ph
 // g_amb is carried by light 0 only (zeros in the other slots).  L == 0: one slot per camera with the ambient term alone.
 constexpr int LS_W = 16, LS_KD = 0, LS_KS = 3, LS_VEC = 6, LS_AMB = 9;
 
-struct PhongLightArgs {
-    const float *grad_out, *world, *normals, *rgb;   // (P,3), (Pw,3), (Pw,3), (P,3)
-    const int64_t *first_idx, *num_pts;
-    int shared, L, point_lights;
-    int64_t Pw, P;
-    const float *kd, *ks, *lvec, *cam;               // (N,L,3), (N,L,3), (N,L,3), (N,3)
-    float shininess;
-};
-
 // Stage 1 of dss_phong_backward_lights: workgroup (b, n, l) sums ONE light's terms over its share of camera n's pairs, one
 // pair per lane and sweep; gridDim.z = max(L, 1) and its partial lands in slot n * gridDim.z + l, so that stage 2 sees the
 // slots as rows.  L is a launch dimension, not a template argument, so the cost per thread does not depend on it: 12 live
-// fp32 accumulators (the pad of the slot is a constant zero) next to the ~40 values of one pair and one light -- 69 VGPRs
+// fp32 accumulators (the pad of the slot is a constant zero) next to the ~40 values of one pair and one light -- 72 VGPRs
 // as compiled for gfx950, no scratch -- and 64 floats of LDS per WORKGROUP (block_sum_store<16>), a quarter of a float per
 // thread.  The price is that every light re-reads the pair (48 bytes) and re-normalises n^ and v^; accumulating all lights
 // in one pass would need 9 L + 3 accumulators per thread, i.e. either a kernel per L or 16 L floats of LDS per thread.
-// The pair's D, S and gdv (d loss / d d^) are RESTATED from phong_kernel<true> (shading.hip) operation by operation, like
-// phong_camera_partial_kernel's gv, for the one light of this workgroup: the sums over lights of that kernel (dif, spec, gn,
-// gv) do not reach these outputs.
-__global__ __launch_bounds__(RB_BLOCK) void phong_light_partial_kernel(const PhongLightArgs A, int sweeps,
-                                                                       float *__restrict__ partials)
+// The pair's D, S and gdv (d loss / d d^) are those of phong_kernel<true> (shading.hip) through phong.h, for the one light
+// of this workgroup: the sums over lights of that kernel (dif, spec, gn, gv) do not reach these outputs.
+__global__ __launch_bounds__(RB_BLOCK) void phong_light_partial_kernel(const PhongArgs A, const float *__restrict__ grad_out,
+                                                                       int sweeps, float *__restrict__ partials)
 {
     const int n = blockIdx.y, l = blockIdx.z;
     float acc[LS_W];
@@ -266,7 +217,7 @@ __global__ __launch_bounds__(RB_BLOCK) void phong_light_partial_kernel(const Pho
         const int64_t wi = A.shared ? p - f : p;
         if (wi >= A.Pw) continue;
         const float c[3] = {A.rgb[3 * p], A.rgb[3 * p + 1], A.rgb[3 * p + 2]};
-        const float g[3] = {A.grad_out[3 * p], A.grad_out[3 * p + 1], A.grad_out[3 * p + 2]};
+        const float g[3] = {grad_out[3 * p], grad_out[3 * p + 1], grad_out[3 * p + 2]};
         if (l == 0) {                                           // out = c * (ambient + ...) + ...
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) acc[LS_AMB + ch] += g[ch] * c[ch];
@@ -274,25 +225,15 @@ __global__ __launch_bounds__(RB_BLOCK) void phong_light_partial_kernel(const Pho
         if (A.L == 0) continue;
         const float x[3] = {A.world[3 * wi], A.world[3 * wi + 1], A.world[3 * wi + 2]};
         const float m[3] = {A.normals[3 * wi], A.normals[3 * wi + 1], A.normals[3 * wi + 2]};
-        const float mn = cam_safe_norm(m[0], m[1], m[2]);
-        const float nh[3] = {m[0] / mn, m[1] / mn, m[2] / mn};
         const float w[3] = {A.cam[3 * n] - x[0], A.cam[3 * n + 1] - x[1], A.cam[3 * n + 2] - x[2]};
-        const float wn = cam_safe_norm(w[0], w[1], w[2]);
-        const float v[3] = {w[0] / wn, w[1] / wn, w[2] / wn};
-        const float *lv = A.lvec + ((size_t)n * A.L + l) * 3;
+        float nh[3], v[3];
+        unit(m, nh);
+        unit(w, v);
         const float *kd = A.kd + ((size_t)n * A.L + l) * 3;
         const float *ks = A.ks + ((size_t)n * A.L + l) * 3;
-        float u[3] = {lv[0], lv[1], lv[2]};
-        if (A.point_lights) { u[0] -= x[0]; u[1] -= x[1]; u[2] -= x[2]; }
-        const float un = cam_safe_norm(u[0], u[1], u[2]);
-        const float d[3] = {u[0] / un, u[1] / un, u[2] / un};
-        const float ca = nh[0] * d[0] + nh[1] * d[1] + nh[2] * d[2];
-        const float r[3] = {-d[0] + 2.0f * (ca * nh[0]), -d[1] + 2.0f * (ca * nh[1]), -d[2] + 2.0f * (ca * nh[2])};
-        const float a0 = v[0] * r[0] + v[1] * r[1] + v[2] * r[2];
-        const bool lit = ca > 0.0f;
-        const float alpha = lit ? fmaxf(a0, 0.0f) : 0.0f;
-        const float D = fmaxf(ca, 0.0f);
-        const float S = powf(alpha, A.shininess);
+        const PhongLight t = phong_light(A, n, l, x, nh, v);
+        const float D = fmaxf(t.ca, 0.0f);
+        const float S = powf(t.alpha, A.shininess);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             acc[LS_KD + ch] += g[ch] * c[ch] * D;               // dif += kd * D, out = c * (... + dif)
@@ -300,17 +241,9 @@ __global__ __launch_bounds__(RB_BLOCK) void phong_light_partial_kernel(const Pho
         }
         const float gd = g[0] * c[0] * kd[0] + g[1] * c[1] * kd[1] + g[2] * c[2] * kd[2];   // d loss / d D
         const float gs = g[0] * ks[0] + g[1] * ks[1] + g[2] * ks[2];                        // d loss / d S
-        float gca = lit ? gd : 0.0f;
-        const float ga0 = (lit && a0 > 0.0f) ? gs * A.shininess * powf(alpha, A.shininess - 1.0f) : 0.0f;
-        float gdv[3];  // d loss / d d^
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gdv[i] = -ga0 * v[i];       // r = -d^ + ...
-        const float gr_n = ga0 * (v[0] * nh[0] + v[1] * nh[1] + v[2] * nh[2]);
-        gca += 2.0f * gr_n;                                     // r = ... + 2 ca n^
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gdv[i] += gca * nh[i];
-        float gu[3];
-        cam_normalize_backward(u, gdv, gu);                     // u = location - x, or the direction itself
+        float gdv[3], gu[3];  // d loss / d d^, d u
+        phong_gdv(t, nh, v, gd, phong_ga0(t, gs, A.shininess), gdv);
+        normalize_backward(t.u, gdv, gu);                       // u = location - x, or the direction itself
 #pragma unroll
         for (int i = 0; i < 3; ++i) acc[LS_VEC + i] += gu[i];
     }
@@ -437,33 +370,30 @@ extern "C" int dss_phong_backward_camera(const float *grad_out, const float *wor
                                          const float *light_vec, int L, int point_lights, const float *cam_center,
                                          float shininess, float *grad_cam, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (N <= 0 || N > 65535 || Pw < 0 || L < 0) {
+    if (N > 65535) {                                            // cameras are gridDim.y
         set_error("dss_phong_backward_camera: bad sizes N=%d Pw=%lld L=%d", N, (long long)Pw, L);
         return DSS_ERR_INVALID_ARGUMENT;
     }
-    if (!first_idx || !num_pts || !cam_center || !grad_cam ||
-        (Pw > 0 && (!grad_out || !world || !normals || !rgb || !ambient ||
-                    (L > 0 && (!diffuse_color || !specular_color || !light_vec))))) {
+    PhongArgs A;
+    int rc = phong_args("dss_phong_backward_camera", A, world, normals, rgb, first_idx, num_pts, N, Pw, shared_cloud, ambient,
+                        diffuse_color, specular_color, light_vec, L, point_lights, cam_center, shininess);
+    if (rc) return rc;
+    if (!first_idx || !num_pts || !cam_center || !grad_cam || (Pw > 0 && !grad_out)) {   // needed without points as well
         set_error("dss_phong_backward_camera: NULL tensor pointer");
         return DSS_ERR_INVALID_ARGUMENT;
     }
-    const int64_t P = shared_cloud ? (int64_t)N * Pw : Pw;
     const ReducePlan pl = reduce_plan(Pw);
     const int blocks = Pw > 0 ? pl.blocks : 0;
-    const size_t need = dss_camera_backward_workspace(N, P);   // >= N * blocks * 4 floats
+    const size_t need = dss_camera_backward_workspace(N, A.P);   // >= N * blocks * 4 floats
     if (!workspace || workspace_bytes < need) {
         set_error("dss_phong_backward_camera: workspace %zu bytes < required %zu", workspace_bytes, need);
         return DSS_ERR_INVALID_ARGUMENT;
     }
     float *partials = static_cast<float *>(workspace);
     if (blocks > 0) {
-        PhongCamArgs A;
-        A.grad_out = grad_out; A.world = world; A.normals = normals; A.first_idx = first_idx; A.num_pts = num_pts;
-        A.shared = shared_cloud; A.L = L; A.point_lights = point_lights; A.Pw = Pw; A.P = P; A.ks = specular_color;
-        A.lvec = light_vec; A.cam = cam_center; A.shininess = shininess;
         hipLaunchKernelGGL(phong_camera_partial_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(RB_BLOCK), 0, as_stream(stream),
-                           A, pl.sweeps, partials);
-        const int rc = check_launch("dss_phong_backward_camera");
+                           A, grad_out, pl.sweeps, partials);
+        rc = check_launch("dss_phong_backward_camera");
         if (rc) return rc;
     }
     hipLaunchKernelGGL((sum_partials_kernel<4, false>), dim3((unsigned)N), dim3(RB_BLOCK), 0, as_stream(stream), partials, blocks,
@@ -487,34 +417,31 @@ extern "C" int dss_phong_backward_lights(const float *grad_out, const float *wor
                                          float shininess, float *grad_ambient, float *grad_diffuse, float *grad_specular,
                                          float *grad_light_vec, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (N <= 0 || N > 65535 || Pw < 0 || L < 0 || L > 65535) {
+    if (N > 65535 || L > 65535) {                               // cameras are gridDim.y, lights gridDim.z
         set_error("dss_phong_backward_lights: bad sizes N=%d Pw=%lld L=%d", N, (long long)Pw, L);
         return DSS_ERR_INVALID_ARGUMENT;
     }
-    if (!first_idx || !num_pts || !cam_center ||
-        (Pw > 0 && (!grad_out || !world || !normals || !rgb || !ambient ||
-                    (L > 0 && (!diffuse_color || !specular_color || !light_vec))))) {
+    PhongArgs A;
+    int rc = phong_args("dss_phong_backward_lights", A, world, normals, rgb, first_idx, num_pts, N, Pw, shared_cloud, ambient,
+                        diffuse_color, specular_color, light_vec, L, point_lights, cam_center, shininess);
+    if (rc) return rc;
+    if (!first_idx || !num_pts || !cam_center || (Pw > 0 && !grad_out)) {                 // needed without points as well
         set_error("dss_phong_backward_lights: NULL tensor pointer");
         return DSS_ERR_INVALID_ARGUMENT;
     }
-    const int64_t P = shared_cloud ? (int64_t)N * Pw : Pw;
     const ReducePlan pl = reduce_plan(Pw);
     const int blocks = Pw > 0 ? pl.blocks : 0;
     const int slots = L > 0 ? L : 1;
-    const size_t need = dss_phong_backward_lights_workspace(N, P, L);   // >= N * slots * blocks * 16 floats
+    const size_t need = dss_phong_backward_lights_workspace(N, A.P, L);   // >= N * slots * blocks * 16 floats
     if (!workspace || workspace_bytes < need) {
         set_error("dss_phong_backward_lights: workspace %zu bytes < required %zu", workspace_bytes, need);
         return DSS_ERR_INVALID_ARGUMENT;
     }
     float *partials = static_cast<float *>(workspace);
     if (blocks > 0) {
-        PhongLightArgs A;
-        A.grad_out = grad_out; A.world = world; A.normals = normals; A.rgb = rgb; A.first_idx = first_idx; A.num_pts = num_pts;
-        A.shared = shared_cloud; A.L = L; A.point_lights = point_lights; A.Pw = Pw; A.P = P; A.kd = diffuse_color;
-        A.ks = specular_color; A.lvec = light_vec; A.cam = cam_center; A.shininess = shininess;
         hipLaunchKernelGGL(phong_light_partial_kernel, dim3((unsigned)blocks, (unsigned)N, (unsigned)slots), dim3(RB_BLOCK), 0,
-                           as_stream(stream), A, pl.sweeps, partials);
-        const int rc = check_launch("dss_phong_backward_lights");
+                           as_stream(stream), A, grad_out, pl.sweeps, partials);
+        rc = check_launch("dss_phong_backward_lights");
         if (rc) return rc;
     }
     hipLaunchKernelGGL(sum_light_partials_kernel, dim3((unsigned)N * (unsigned)slots), dim3(RB_BLOCK), 0, as_stream(stream),

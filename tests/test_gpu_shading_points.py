@@ -214,6 +214,92 @@ def test_the_three_phong_kernels_agree(name, kind, shin):
     assert ratio <= bar, (ratio, bar)
 
 
+def _pair_case(N, Pw, shared, L, seed=5):
+    """A case (in the order of `sr.layout_case`) in which every (camera, point, light) is lit with a0 > 0: the points near
+    the origin with normals about +z, the cameras and the lights (locations or directions alike) above them.  Not shared:
+    N clouds of ONE point each (Pw = N)."""
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    u = lambda *s: torch.rand(*s, generator=g)
+    P = N * Pw if shared else Pw
+    up = torch.tensor([0.0, 0.0, 1.0])
+    world, normals = 0.2 * r(Pw, 3), 1.7 * (up + 0.2 * r(Pw, 3))
+    rgb, grad_out = u(P, 3), r(P, 3)
+    amb, kd, ks = u(N, 3) * 0.5, u(N, L, 3), u(N, L, 3)
+    lvec, cam = 2.5 * up + 0.4 * r(N, L, 3), 3.0 * up + 0.4 * r(N, 3)
+    per = Pw if shared else 1
+    first, num = torch.arange(N, dtype=torch.int64) * per, torch.full((N,), per, dtype=torch.int64)
+    return (world, normals, rgb, first, num, amb, kd, ks, lvec, cam, grad_out), shared
+
+
+def _all_lit(case, shared, point):
+    """ca > 0.5 and a0 > 0.5 for every (camera, point, light) of the case (fp64, on the CPU)"""
+    world, normals, _rgb, first, num, _amb, _kd, _ks, lvec, cam, _g = [t.double() if t.is_floating_point() else t for t in case]
+    unit = lambda t: torch.nn.functional.normalize(t, dim=1)
+    for n in range(len(num)):
+        rows = slice(0, int(num[n])) if shared else slice(int(first[n]), int(first[n] + num[n]))
+        x, nh = world[rows], unit(normals[rows])
+        v = unit(cam[n][None] - x)
+        for l in range(lvec.shape[1]):
+            d = unit(lvec[n, l][None] - x if point else lvec[n, l][None].expand_as(x))
+            ca = (nh * d).sum(1, keepdim=True)
+            a0 = (v * (-d + 2.0 * ca * nh)).sum(1)
+            if not (float(ca.min()) > 0.5 and float(a0.min()) > 0.5):
+                return False
+    return True
+
+
+def _three_kernels(case, shared, point, shin):
+    """-> grad_world (Pw,3), grad_cam (N,3), (grad_ambient, grad_diffuse, grad_specular, grad_light_vec)"""
+    args = _dev(case)
+    a = (args[10], *args[:9], point, args[9], float(shin), shared)
+    return ops.phong_backward(*a)[0], ops.phong_backward_camera(*a), ops.phong_backward_lights(*a)
+
+
+@pytest.mark.parametrize("shin", [12.0, 64.0])
+def test_one_pair_links_the_three_kernels_bit_for_bit(shin):
+    """With a single pair per camera every reduction tree adds one value to zeros, so the pair's gw = J(w)^T gv and
+    gu = J(u)^T gdv of phong_kernel<true>, phong_camera_partial_kernel and phong_light_partial_kernel (one statement of
+    the arithmetic: csrc/phong.h) meet under `torch.equal`: grad_world = 0 - gu - gw per camera in turn."""
+    # three clouds of one point each, two directional lights: only the view direction reaches the position
+    case, shared = _pair_case(3, 3, False, 2)
+    assert _all_lit(case, shared, False)
+    gw, gcam, _gl = _three_kernels(case, shared, False, shin)
+    assert bool((gw != 0).all()) and bool((gcam != 0).all())
+    assert torch.equal(gw, -gcam)
+    # the same layout, one point light: the light's location moves with the point as well
+    case, shared = _pair_case(3, 3, False, 1)
+    assert _all_lit(case, shared, True)
+    gw, gcam, gl = _three_kernels(case, shared, True, shin)
+    assert bool((gw != 0).all()) and bool((gcam != 0).all()) and bool((gl[3] != 0).all())
+    assert torch.equal(gw, -(gl[3][:, 0] + gcam))
+    # one point shared by two cameras, directional lights: the cameras in order
+    case, shared = _pair_case(2, 1, True, 2)
+    assert _all_lit(case, shared, False)
+    gw, gcam, _gl = _three_kernels(case, shared, False, shin)
+    assert bool((gw != 0).all()) and bool((gcam != 0).all())
+    assert torch.equal(gw[0], -(gcam[0] + gcam[1]))
+
+
+@pytest.mark.parametrize("kind,shin", KIND_SHIN)
+def test_one_pair_links_the_specular_gradient_to_the_forward_bit_for_bit(kind, shin):
+    """ambient 0, kd = 0, ks = 1: `out` of phong_kernel<false> is S of the pair's one light, and grad_specular of
+    phong_light_partial_kernel is grad_out * S, one light at a time"""
+    case, shared = _pair_case(3, 3, False, 2)
+    point = kind == "point"
+    assert _all_lit(case, shared, point)
+    world, normals, rgb, first, num, amb, kd, ks, lvec, cam, grad_out = case
+    case = (world, normals, rgb, first, num, amb * 0, kd * 0, ks * 0 + 1, lvec, cam, grad_out)
+    g_spec = _three_kernels(case, shared, point, shin)[2][2]
+    assert bool((g_spec != 0).all())
+    world, normals, rgb, first, num, amb, kd, ks, lvec, cam, grad_out = _dev(case)
+    for l in range(2):
+        one = slice(l, l + 1)
+        S = ops.phong_forward(world, normals, rgb, first, num, amb, kd[:, one], ks[:, one], lvec[:, one], point, cam, shin,
+                              shared)
+        assert bool((S != 0).all()) and torch.equal(g_spec[:, l], grad_out * S)
+
+
 @pytest.mark.parametrize("name", ["ragged", "shared3"])
 def test_null_outputs_and_reproducibility(name):
     case, shared = sr.layout_case(name)
