@@ -36,11 +36,12 @@ def calling_thread_backward():
         torch.autograd.set_multithreading_enabled(was)
 
 
-_CLOUD_OPS = ("upsample", "upsample_clouds", "remove_outliers")
+_CLOUD_OPS = ("upsample", "upsample_clouds", "remove_outliers", "denoise_normals", "project_to_latent_surface")
 
 
 def __getattr__(name):
-    """``dss_amd.upsample`` / ``upsample_clouds`` / ``remove_outliers`` (dss_amd/cloud_ops.py), imported on first use so that
+    """``dss_amd.upsample`` / ``upsample_clouds`` / ``remove_outliers`` / ``denoise_normals`` / ``project_to_latent_surface``
+    (dss_amd/cloud_ops.py), imported on first use so that
     ``import dss_amd`` itself stays free of torch."""
     if name in _CLOUD_OPS:
         from . import cloud_ops

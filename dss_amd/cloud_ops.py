@@ -1,9 +1,12 @@
-"""Operators that change the NUMBER of points of a cloud: `upsample` / `upsample_clouds` insert points where a neighbourhood
-is sparsest (DSS/core/cloud.py:555-632), `remove_outliers` drops the points whose neighbourhood is not flat (:363-378).
-Both sit on the exact grid kNN (``ops.knn_points``); the K x K sparsity search and the assembly of the grown cloud are the
-HIP kernels of ``dss_amd/csrc/upsample.hip``, the curvature test reads ``ops.local_frames``.  DESIGN 4.14 states the
-round's contract, tie rules included.  Nothing here is differentiable: the reference uses these tools to re-parametrise
-a model between optimiser phases.
+"""Operators on a whole cloud between optimiser phases.  Those that change the NUMBER of points: `upsample` /
+`upsample_clouds` insert points where a neighbourhood is sparsest (DSS/core/cloud.py:555-632), `remove_outliers` drops the
+points whose neighbourhood is not flat (:363-378).  Both sit on the exact grid kNN (``ops.knn_points``); the K x K sparsity
+search and the assembly of the grown cloud are the HIP kernels of ``dss_amd/csrc/upsample.hip``, the curvature test reads
+``ops.local_frames``.  DESIGN 4.14 states the round's contract, tie rules included.  Those that CLEAN a cloud:
+`denoise_normals` filters the normals over a neighbourhood (:515-552) and `project_to_latent_surface` moves every point
+onto a locally fitted implicit surface (RIMLS, :442-513); their kernels are ``dss_amd/csrc/smoothing.hip``, their contract
+is DESIGN 4.15.  Nothing here is differentiable: the reference uses these tools to re-parametrise a model between optimiser
+phases.
 """
 from typing import List, Optional, Sequence, Union
 
@@ -204,3 +207,126 @@ def remove_outliers(point_clouds, neighborhood_size: int = 16, tolerance: float 
     keeps = list(torch.split(keep, sizes, dim=0))
     pick = lambda lst: None if lst is None else [t[k] for t, k in zip(lst, keeps)]
     return PointClouds3D(pick(pts), pick(point_clouds.normals_list()), pick(point_clouds.features_list()))
+
+
+def _smoothing_inputs(who: str, points, normals, num_points, K: int, search_radius):
+    """Shapes, sizes and refusals that the two cleaning tools share -> (points (N,P,3), normals (N,P,3), sizes).  Nothing is
+    launched here."""
+    if isinstance(points, PointClouds3D):
+        if normals is None:
+            normals = points.normals_padded()
+        if num_points is None:
+            num_points = [int(p.shape[0]) for p in points.points_list()]
+        points = points.points_padded()
+    if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3:
+        raise ValueError("%s expects padded points (N,P,3) or a PointClouds3D" % who)
+    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape):
+        raise ValueError("%s expects normals of the points' shape %s" % (who, tuple(points.shape)))
+    N, P = points.shape[0], points.shape[1]
+    if K < 1 or K + 1 > MAX_KNN:
+        raise ValueError("%s: neighborhood_size must be in 1 .. %d (it searches K + 1 <= %d neighbours), got %d"
+                         % (who, MAX_KNN - 1, MAX_KNN, K))
+    if search_radius is not None and not float(search_radius) > 0.0:
+        raise ValueError("%s: search_radius must be positive, got %r" % (who, search_radius))
+    sizes = _host_ints(P if num_points is None else num_points, N, "num_points")
+    if any(s < 0 or s > P for s in sizes):
+        raise ValueError("num_points must lie in 0 .. P = %d" % P)
+    if not points.is_cuda or not normals.is_cuda:
+        bad = points if not points.is_cuda else normals
+        raise RuntimeError("dss_amd: %s is on %s; the HIP path needs GPU tensors (no CPU fallback)"
+                           % ("points" if bad is points else "normals", bad.device))
+    return points.detach(), normals.detach(), sizes
+
+
+def _search_radius(points, sizes: Sequence[int], c: float, K: int, search_radius) -> torch.Tensor:
+    """(N,) fp32 on the device: ``search_radius`` when given, else min(c K sqrt(diag_n / P_n), 0.2) with diag_n the length
+    of the bounding-box diagonal of cloud n alone (cloud.py:449-451, 522-525).  No device-to-host read."""
+    if search_radius is not None:
+        return torch.full((len(sizes),), float(search_radius), dtype=torch.float32, device=points.device)
+    r = torch.full((len(sizes),), 0.2, dtype=torch.float32, device=points.device)   # an empty cloud: unused
+    for n, s in enumerate(sizes):
+        if s > 0:
+            x = points[n, :s].to(torch.float32)
+            diag = (x.amax(dim=0) - x.amin(dim=0)).norm()
+            r[n] = (float(c * K) * torch.sqrt(diag / float(s))).clamp(max=0.2)
+    return r
+
+
+def _packed_lists(points, normals, sizes, K: int):
+    dev = points.device
+    pts = _pack(points.to(torch.float32), sizes).contiguous()
+    nrm = _pack(normals.to(torch.float32), sizes).contiguous()
+    first, num = _ranges(sizes, dev)
+    knn_d, knn_idx = ops.knn_points(pts, first, num, K + 1)
+    return pts, nrm, first, num, knn_d, knn_idx
+
+
+@torch.no_grad()
+def denoise_normals(points, normals=None, num_points=None, sharpness_sigma: float = 30.0, neighborhood_size: int = 16,
+                    search_radius: Optional[float] = None):
+    """Bilateral filter of the normals over the ``neighborhood_size`` nearest points: `denoise_normals` of
+    DSS/core/cloud.py:515-552 -> normals (N,P,3), unit length, a new tensor; padding rows are zeros.
+
+    points, normals (N,P,3) padded with ``num_points`` the N lengths (None: all P), or a ``PointClouds3D`` (then
+    ``normals=None`` takes the cloud's own).  A neighbour counts if it lies within ``search_radius``, by default
+    min(4 K sqrt(diag / P_n), 0.2) per cloud; its weight is exp(-((1 - n_j.n) / sharpness_sigma)^2) times
+    exp(-|q_j - p|^2 P_n / 2) cut at |q_j - p|^2 <= 32 / P_n.  DESIGN 4.15 states the contract and the two deviations
+    from the reference: a neighbour outside the radius contributes nothing (the reference gathers zeros for it), and a
+    point without any weight keeps its normalised normal (the reference returns a zero vector).  Every cloud is processed
+    as if it were alone.
+
+    Not differentiable.  With sizes given as Python integers the call reads nothing back from the device.  Raises
+    ValueError, before anything is launched, for wrong shapes, K outside 1 .. 39, ``search_radius <= 0`` and
+    ``sharpness_sigma <= 0``.  GPU tensors only: there is no CPU fallback."""
+    K = int(neighborhood_size)
+    if not float(sharpness_sigma) > 0.0:
+        raise ValueError("denoise_normals: sharpness_sigma must be positive, got %r" % (sharpness_sigma,))
+    points, normals, sizes = _smoothing_inputs("denoise_normals", points, normals, num_points, K, search_radius)
+    radius = _search_radius(points, sizes, 4.0, K, search_radius)
+    pts, nrm, first, num, knn_d, knn_idx = _packed_lists(points, normals, sizes, K)
+    out = ops.denoise_normals(pts, nrm, knn_d, knn_idx, first, num, radius, K, float(sharpness_sigma))
+    return _pad_to(out, sizes, points.shape[1])
+
+
+@torch.no_grad()
+def project_to_latent_surface(points, normals=None, num_points=None, sharpness_angle: float = 60.0,
+                              neighborhood_size: int = 31, max_proj_iters: int = 10, max_est_iter: int = 5,
+                              search_radius: Optional[float] = None, return_converged: bool = False):
+    """Move every point onto the implicit surface fitted to its neighbourhood (robust implicit MLS):
+    `project_to_latent_surface` of DSS/core/cloud.py:442-513 -> points (N,P,3), a new tensor (the input is not modified;
+    padding rows are zeros), and with ``return_converged`` also (N,P) bool: the points that stopped moving (a step shorter
+    than 5e-4, or no usable neighbourhood; padding rows False).
+
+    ``max_proj_iters`` outer iterations, each ``max_est_iter`` reweighting passes over the ``neighborhood_size`` nearest
+    points of the INPUT cloud within ``search_radius`` (default min(16 K sqrt(diag / P_n), 0.2) per cloud); every
+    iteration moves the points that have not converged by f grad f of the fitted function, all at once.  ``normals``
+    should be filtered first (`denoise_normals`).  ``sharpness_angle`` is accepted and unused, as in the reference.  DESIGN
+    4.15 states the arithmetic; it improves planar and gently curved clouds and inflates sparse, strongly curved ones.
+
+    Not differentiable.  The iterations are launched back to back; with sizes given as Python integers nothing is read
+    back from the device.  Raises ValueError, before anything is launched, for wrong shapes, K outside 1 .. 39,
+    ``max_proj_iters < 1``, ``max_est_iter < 1`` and ``search_radius <= 0``.  GPU tensors only: no CPU fallback."""
+    K = int(neighborhood_size)
+    if int(max_proj_iters) < 1 or int(max_est_iter) < 1:
+        raise ValueError("project_to_latent_surface: max_proj_iters and max_est_iter must be at least 1, got %r and %r"
+                         % (max_proj_iters, max_est_iter))
+    points, normals, sizes = _smoothing_inputs("project_to_latent_surface", points, normals, num_points, K, search_radius)
+    radius = _search_radius(points, sizes, 16.0, K, search_radius)
+    pts, nrm, first, num, knn_d, knn_idx = _packed_lists(points, normals, sizes, K)
+    live = None
+    for _ in range(int(max_proj_iters)):
+        pts, live = ops.rimls_step(pts, nrm, knn_d, knn_idx, first, num, radius, K, live, int(max_est_iter))
+    out = _pad_to(pts, sizes, points.shape[1])
+    if not return_converged:
+        return out
+    return out, _pad_to(live == 0, sizes, points.shape[1])
+
+
+def _pad_to(packed, sizes, P: int):
+    """`_pad` to a given row count P >= max(sizes)."""
+    out = packed.new_zeros((len(sizes), P) + tuple(packed.shape[1:]))
+    f = 0
+    for n, s in enumerate(sizes):
+        out[n, :s] = packed[f:f + s]
+        f += s
+    return out

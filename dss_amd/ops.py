@@ -1364,3 +1364,6 @@ def image_loss_band_backward_partials(rgba_band, target_rgb, target_mask, rows, 
 from .cross_cloud import chamfer_backward, chamfer_order, nearest_points, packed_cloud_ids  # noqa: E402,F401
 # likewise the two kernels of an upsampling round (upsample_ops.py; the rounds themselves are dss_amd.cloud_ops.upsample)
 from .upsample_ops import upsample_candidates, upsample_insert  # noqa: E402,F401
+# and the two kernels that clean a cloud (smoothing_ops.py; the public calls are dss_amd.cloud_ops.denoise_normals and
+# project_to_latent_surface)
+from .smoothing_ops import denoise_normals, rimls_step  # noqa: E402,F401

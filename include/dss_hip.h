@@ -618,6 +618,52 @@ DSS_API int dss_upsample_insert(const float *points /* (P,3) */, const float *at
                                 float *out_attrs /* (P_out,C) or NULL */, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cleaning a cloud: the bilateral filter of the normals (`denoise_normals`, DSS/core/cloud.py:515-552) and the robust
+ * implicit MLS projection (`project_to_latent_surface`, :442-513), one outer iteration per call.  The reference
+ * materialises (N,P,K,3) tensors in dozens of launches per pass and synchronises the host in every pass; here a group of
+ * 8 lanes keeps a point's neighbourhood in registers for all passes of a call and nothing is read back.
+ * Neighbourhood (both entries): knn_dists / knn_idx (P, K + 1) = the lists of dss_knn_points(K + 1); the neighbours of p
+ * are entries 1 .. K (self dropped).  Entry j is LIVE iff j < num_pts[n] - 1 (a real point, not the zero padding of a
+ * short list) and knn_dists[p][1 + j] < radius[n]^2, the square taken in fp32; radius (N,) fp32 is the search radius of
+ * every cloud (the reference's min(c K sqrt(diag / P), 0.2), c = 4 at :522-525 and 16 at :449-451, is formed by the
+ * caller).  A dead entry contributes NOTHING.  Deviation: the reference gathers zeros for it (frnn_gather), so its
+ * result depends on where the origin lies.
+ * dss_denoise_normals, with n = normalize(normals[p]), n_j / q_j the normalised normal / position of a live neighbour
+ * (F.normalize, eps 1e-12):
+ *   wn_j = exp(-((1 - n_j . n) / sharpness_sigma)^2)     (the reference's code divides by the raw sigma, :537-538)
+ *   inv = P_n / 2, dp_j = |q_j - p|^2                    wp_j = exp(-dp_j inv) if dp_j <= 16 / inv, else 0   (:541-546)
+ *   out[p] = normalize(sum_j wn_j wp_j n_j)
+ * Deviation: a point whose weights sum to 0 keeps its normalised input normal (the reference returns the zero vector).
+ * Every packed row of out is written; a row that no cloud owns gets zeros.
+ * dss_rimls_step: step t reads ALL positions of step t - 1 from points_in and writes step t to points_out (another
+ * buffer); live_in (P,) uint8 or NULL (the first step: every point) says which points still move, live_out (P,) is
+ * fully written.  `normals` and the lists are those of the INPUT cloud in every step.  A point is live iff live_in says
+ * so AND it has a live neighbour AND d_0 > 0, d_0 = the list distance of its nearest live neighbour (entry 1 of the
+ * ascending list); inv = 1 / (16 d_0) (:460).  A point that is not live keeps its position bit for bit, is still read
+ * by its neighbours, and has live_out = 0; a call on a state without live points changes nothing.  For a live point,
+ * diff_j = p - q_j, fx_j = diff_j . n_j, alpha_j = 1, f = 0, g = 0, repeat max_est_iter times (:475-503; the reference's
+ * inner convergence test never ends a pass early -- it compares a tensor with its own alias -- so this is its
+ * arithmetic):
+ *   from the second pass on   alpha_j = exp(-(|n_j - g| / 0.5)^2) exp(-(fx_j - f)^2 inv / 4)
+ *   phi_j = exp(-|diff_j|^2 inv)      w_j = phi_j alpha_j      gw_j = 2 diff_j (inv phi_j w_j)    (phi enters twice)
+ *   f = sum w_j fx_j / eps_denom(sum w_j)
+ *   g = (sum gw_j fx_j - f sum gw_j + sum w_j n_j) / eps_denom(sum w_j)
+ * then move = f g, p <- p - move, live_out = |move| > 5e-4 (:505-508).  Every sum has a fixed lane order: a repeated call
+ * returns the same bits, whatever else the launch holds.
+ * Refusals (DSS_ERR_INVALID_ARGUMENT, nothing launched): K < 1 or K + 1 > 40; sharpness_sigma <= 0; max_est_iter < 1;
+ * points_out == points_in or live_out == live_in.  The kernels follow no id that leaves its cloud or the packed array.
+ * ------------------------------------------------------------------------------------------- */
+DSS_API int dss_denoise_normals(const float *points /* (P,3) */, const float *normals /* (P,3) */,
+                                const float *knn_dists /* (P,K+1) */, const int64_t *knn_idx /* (P,K+1) */,
+                                const int64_t *first_idx, const int64_t *num_pts, const float *radius /* (N,) */, int N,
+                                int64_t P, int K, float sharpness_sigma, float *out_normals /* (P,3) */, void *stream);
+DSS_API int dss_rimls_step(const float *points_in /* (P,3) */, const float *normals /* (P,3) */,
+                           const float *knn_dists /* (P,K+1) */, const int64_t *knn_idx /* (P,K+1) */,
+                           const int64_t *first_idx, const int64_t *num_pts, const float *radius /* (N,) */,
+                           const uint8_t *live_in /* (P,) or NULL */, int N, int64_t P, int K, int max_est_iter,
+                           float *points_out /* (P,3) */, uint8_t *live_out /* (P,) */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Phong shading of the points = LightingTexture.forward (DSS/core/texture.py:65-125):
  * apply_lighting (:26-63) with lighting.py:10-77 (diffuse) and :80-172 (specular) for L PointLights
  * (point_lights = 1: light_vec = location, direction = location - point, lighting.py:239-302) or
