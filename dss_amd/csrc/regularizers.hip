@@ -227,10 +227,12 @@ __global__ __launch_bounds__(256) void points_inmask_kernel(const float *__restr
         const float X = ((x * m[0] + y * m[4]) + z * m[8]) + m[12];
         const float Y = ((x * m[1] + y * m[5]) + z * m[9]) + m[13];
         const float Wc = ((x * m[3] + y * m[7]) + z * m[11]) + m[15];
-        const float gx = fminf(fmaxf(-(X / Wc), -1.0f), 1.0f), gy = fminf(fmaxf(-(Y / Wc), -1.0f), 1.0f);
+        const float px = -(X / Wc), py = -(Y / Wc);
+        if (!(px == px && py == py)) continue;  // NaN position (a NaN coordinate, 0/0): never in mask.  Tested BEFORE the
+                                                // clamp: fmaxf / fminf return their non-NaN operand
+        const float gx = fminf(fmaxf(px, -1.0f), 1.0f), gy = fminf(fmaxf(py, -1.0f), 1.0f);
         const float ix = fminf(fmaxf(((gx + 1.0f) * (float)W - 1.0f) / 2.0f, 0.0f), (float)(W - 1));
         const float iy = fminf(fmaxf(((gy + 1.0f) * (float)H - 1.0f) / 2.0f, 0.0f), (float)(H - 1));
-        if (!(ix == ix && iy == iy)) continue;  // NaN projection (w == 0): never in mask
         const int x0 = (int)floorf(ix), y0 = (int)floorf(iy);
         const float fx = ix - (float)x0, fy = iy - (float)y0;  // weight of the +1 taps; 1 - f of the others
         const float *img = mask + (size_t)n * H * W;

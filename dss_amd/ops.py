@@ -1043,9 +1043,15 @@ def _mask_u8(mask, name, P, dev):
     mask = _lib.require_gpu(mask, name)
     if mask.numel() != P:
         raise RuntimeError("dss_amd: %s must have one entry per packed point (%d), got %d" % (name, P, mask.numel()))
-    if mask.dtype == torch.bool:
-        return mask.contiguous().view(torch.uint8)   # same bytes: no conversion kernel
-    return mask.to(torch.uint8).contiguous()
+    return _nonzero_u8(mask)
+
+
+def _nonzero_u8(mask):
+    """Flags of any dtype as 0 / 1 bytes, true where the reference's ``.bool()`` is: ``!= 0`` (0.5 and 256.0 are true; a
+    cast to uint8 would make them 0).  bool keeps its bytes: no conversion kernel."""
+    if mask.dtype != torch.bool:
+        mask = mask != 0
+    return mask.contiguous().view(torch.uint8)
 
 
 def _knn_lists(knn_dists, knn_idx, P, need_dists=True):

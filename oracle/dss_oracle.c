@@ -1046,8 +1046,9 @@ DSS_ORACLE_API void oracle_points_inmask(const float *points /* (P,3) */, const 
             const float X = ((x * m[0] + y * m[4]) + z * m[8]) + m[12];
             const float Y = ((x * m[1] + y * m[5]) + z * m[9]) + m[13];
             const float Wc = ((x * m[3] + y * m[7]) + z * m[11]) + m[15];
-            const float gx = fminf(fmaxf(-(X / Wc), -1.0f), 1.0f), gy = fminf(fmaxf(-(Y / Wc), -1.0f), 1.0f);
-            if (!(gx == gx && gy == gy)) continue;
+            const float px = -(X / Wc), py = -(Y / Wc);
+            if (!(px == px && py == py)) continue; /* a NaN position is never in mask; fmaxf would swallow the NaN */
+            const float gx = fminf(fmaxf(px, -1.0f), 1.0f), gy = fminf(fmaxf(py, -1.0f), 1.0f);
             in = grid_sample_bilinear_reflect(mask + (size_t)n * H * W, H, W, gx, gy) != 0.0f;
         }
         inmask[p] = (uint8_t)(in && (!visible || visible[p]));

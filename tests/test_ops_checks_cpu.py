@@ -133,6 +133,15 @@ def test_shape_checks_that_precede_the_device_checks():
         ops._splat_points_occ_backward(z(P, 2), rad, occ, first, num, 5.0)
 
 
+def test_non_bool_masks_are_true_where_nonzero():
+    """`keep` / `visible` of any dtype mean what the reference's .bool() means; .to(uint8) made 0.5 and 256.0 false"""
+    vals = [0.0, 0.5, 256.0, -1.0, -0.0, float("nan"), 1.0]
+    assert ops._nonzero_u8(torch.tensor(vals)).tolist() == [int(b) for b in torch.tensor(vals).bool().tolist()] == [0, 1, 1, 1, 0, 1, 1]
+    assert ops._nonzero_u8(torch.tensor([0, 256, 3], dtype=i32)).tolist() == [0, 1, 1]
+    flags = torch.tensor([True, False, True])
+    assert ops._nonzero_u8(flags).dtype == torch.uint8 and ops._nonzero_u8(flags).data_ptr() == flags.data_ptr()
+
+
 def test_rasterize_fine_refuses_foreign_bin_points():
     for foreign in (z(8, dtype=torch.uint8), None, [1, 2]):
         with pytest.raises(RuntimeError, match="a clone / device copy is not accepted"):

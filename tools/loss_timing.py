@@ -1,5 +1,5 @@
 """Time the regulariser chain of one training iteration (trainer.py:319-326): self kNN (K = 12), normal mollification,
-projection loss forward + backward, repulsion loss forward + backward, on one cloud of P points.
+projection loss forward + backward, repulsion loss forward + backward, and the in-mask filter, on one cloud of P points.
 
     python tools/loss_timing.py [P]
 """
@@ -48,6 +48,11 @@ def main():
     out["repulsion_fwd_us"] = timed(lambda: ops.repulsion_loss(X, moll, idx, F, L, 0.75, 2.0))
     out["repulsion_bwd_us"] = timed(lambda: ops.repulsion_loss(X, moll, idx, F, L, 0.75, 2.0, grad_loss=g3,
                                                                want_loss=False, want_grad=True))
+    # in-mask filter of the same iteration (point_modeling.py:188-212): three views, 256 x 256 masks
+    M = torch.eye(4, device=dev).repeat(3, 1, 1)
+    M[:, 2, 3], M[:, 3, 3] = 1.0, 2.0                     # Wc = z + 2
+    mask = (torch.rand(3, 256, 256, device=dev) < 0.5).float()
+    out["inmask_us"] = timed(lambda: ops.points_inmask(X, M, mask, vis))
     # bytes one projection call must move: the (P,K) lists (12 B/entry: d2 + int64 id) + own point/normal + outputs;
     # the neighbour gathers (24 B each) are L2 hits for clouds of this size
     alg = P * (12 * 12 + 24 + 4)
