@@ -86,6 +86,10 @@ extern "C" int dss_set_option(int option, int value)
         dss::set_error("dss_set_option: DSS_OPT_BACKWARD_TPW takes 0 (automatic), 1, 2 or 4");
         return DSS_ERR_INVALID_ARGUMENT;
     }
+    if (option == DSS_OPT_BACKWARD_GRID && value < 0) {
+        dss::set_error("dss_set_option: DSS_OPT_BACKWARD_GRID takes 0 (automatic) or a positive number of workgroups");
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
     dss::g_opt[option].store(value, std::memory_order_relaxed);
     return DSS_OK;
 }

@@ -1118,6 +1118,11 @@ extern "C" __device__ unsigned long long dss_dispatch_id(void) __asm("llvm.amdgc
 #define FB_ALPHA_PER_WG 2048    // pixels of the alpha plane per (256-thread) workgroup of fb_prep_kernel
 #define FB_MAX_SEG 256          // segments of the list (= FB_THREADS: fb_median scans them one per thread)
 #define FB_MEDIAN_LDS (FB_CAND_MAX + FB_HIST + 3 * FB_MAX_SEG + 32)   // words of LDS of fb_median
+// Claim counters of the two-launch form's gather (see "the incomplete last round" in render_backward_kernel): FB_CLAIM_CTRS
+// words, each on a cache line of its own, zeroed by fb_prep_kernel of the same call.
+#define FB_CLAIM_CTRS 128
+#define FB_CLAIM_LINE 32        // words between two counters (128 bytes)
+#define FB_CLAIM_WORDS (FB_CLAIM_CTRS * FB_CLAIM_LINE)
 // level-0 bucket of an order-preserving radius key: 16 octaves [2^-16, 1) of NDC radius in 256 buckets (1/16 octave each;
 // everything below / above lands in the end buckets: any monotone map keeps the selection exact)
 #define FB_KEY_LO 0xB7800000u   // float_key(2^-16)
@@ -1136,6 +1141,7 @@ struct FusedPrep {
     uint32_t *chunk_hist;         // (N, chunks, FB_BUCKETS): EXCLUSIVE prefix of the bucket counts of (cloud, segment)
     uint2 *seg_range;             // (N, chunks): first entry / entries of cloud n inside segment c
     unsigned long long *tags;     // FB_TAGS words
+    uint32_t *claim;              // FB_CLAIM_WORDS: claim counters of the gather's last round (zeroed by fb_prep_kernel)
     float *rs;                    // (N) out
     int64_t P;
     int chunks, per;              // segments (<= 64); points per thread of a segment (segment = per * 256 points)
@@ -1524,6 +1530,9 @@ __global__ __launch_bounds__(FB_THREADS) void fb_prep_kernel(const FusedPrep F, 
         }
         return;
     }
+    // the claim counters of the gather launch that follows: plain stores, published by the kernel boundary (a replayed graph
+    // runs this launch again; the gather itself resets nothing)
+    if (blockIdx.x == 0 && F.claim != nullptr && threadIdx.x < FB_CLAIM_CTRS) F.claim[(size_t)threadIdx.x * FB_CLAIM_LINE] = 0u;
     __shared__ uint32_t s_fb[2 * FB_BUCKETS + 160];
     fb_prep_segment<PER>(F, (int)blockIdx.x, radii, first_idx, num_pts, N, grad_pts, grad_feat, C, s_fb);
 }
@@ -1672,6 +1681,25 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
     __shared__ uint32_t s_deal[2];
     const uint32_t blk4 = (blockIdx.x - first_block) * 4u;
     auto dyn_group = [&](uint32_t i) -> uint32_t { return blk4 + (i & 3u) + (i >> 2) * n_waves; };
+    // PREP && !BAND, occupancy half: the incomplete last round is CLAIMED, not dealt.  The full rounds
+    // [r n_waves, (r + 1) n_waves) stay dealt as above.  When the list ends with a round of fewer than n_waves groups behind at least one full round, a dealt last
+    // round would hand a second (third, ...) group to the workgroups with the lowest indices, however late their blend half
+    // or their first groups ended, and the launch ends with them.  Instead a wavefront that has consumed the last window
+    // trip of its last dealt group takes a ticket from a global counter -- the round trip overlaps its reductions, clip,
+    // projection and stores -- and runs the group of that ticket; a ticket beyond the end of the round means it leaves.
+    // Nobody waits on a counter and the gather never resets one (fb_prep_kernel of the same call zeroes them).  A task's
+    // lanes, loads and summation order do not depend on the wavefront that runs it: the outputs are bit-identical.
+    // Layout: FB_CLAIM_CTRS = 128 counters, 128 bytes apart; counter c owns the groups c, c + 128, ... of the
+    // round and is the counter of the wavefronts w = c mod 128 (the four of a workgroup take four neighbouring counters, and
+    // the wavefronts of one counter sit in workgroups 32 apart: on one XCD).  Arrivals per counter and launch = its
+    // wavefronts + its groups (every claimed group brings its wavefront back once): at the metric's configuration (1,280
+    // workgroups = 5,116 worker wavefronts, 6,611 groups: 1,495 in the last round) 40 + 12 = 52; at most twice its
+    // wavefronts for any list.
+    constexpr bool CLAIM = PREP && !BAND;
+    const uint32_t full_rounds = n_groups / max(n_waves, 1u);
+    const uint32_t claim_base = full_rounds * n_waves;              // first group of the incomplete round
+    const bool claimable = CLAIM && full_rounds >= 1u && claim_base < n_groups;
+    const uint32_t claim_slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave & (FB_CLAIM_CTRS - 1u)));   // (SGPR)
     // ---- BAND: this workgroup's share of the visible list, filtered into LDS ---------------------------------------------
     // share slot t (= thread + 256 j): record arrays [id | cloud << 24, px, py, pz, rx, ry, scaler][BAND_SHARE], loaded ONCE
     // by the filter pass (the tasks of both halves then start from LDS: one dependent memory round trip less per round);
@@ -1774,6 +1802,10 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
     auto run_tasks = [&](auto phase_tag) {
     constexpr int PH = decltype(phase_tag)::value;
     uint32_t t_cur = t_first;
+    // the occupancy half claims its last round; the blend half keeps the dealt one (claims there measured no gain of their own)
+    constexpr bool CL = CLAIM && PH == 2;
+    uint32_t *claim_ctr = CL ? F.claim + (size_t)claim_slot * FB_CLAIM_LINE : nullptr;
+    bool claiming = false;   // uniform: the dealt groups are used up, the current group's successor comes from claim_ctr
     const uint32_t b_groups = BAND ? (s_bcnt[PH == 2 ? 1 : 0] + TPW - 1u) / TPW : 0u;   // groups of this workgroup's own list
     int p_nx = BAND ? band_ids(wave_in_wg, PH == 2 ? 1 : 0) : task_ids(wave_u);
     for (;;) {
@@ -1788,9 +1820,14 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
             if (lane == 0) i_next = atomicAdd(&s_deal[PH == 2 ? 1 : 0], 1u);
             q_next = t_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)i_next);
         } else if (PREP) {
-            uint32_t i_next = 0;
-            if (lane == 0) i_next = atomicAdd(&s_deal[PH == 2 ? 1 : 0], 1u);
-            q_next = t_next = dyn_group((uint32_t)__builtin_amdgcn_readfirstlane((int)i_next));
+            q_next = t_next = 0xffffffffu;
+            if (!(CL && claiming)) {
+                uint32_t i_next = 0;
+                if (lane == 0) i_next = atomicAdd(&s_deal[PH == 2 ? 1 : 0], 1u);
+                i_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)i_next);
+                if (CL && claimable && i_next >= 4u * full_rounds) claiming = true;   // (the workgroup's dealt groups are i < 4 R)
+                else q_next = t_next = dyn_group(i_next);
+            }
         } else {
             t_next = t_cur + t_stride;
             q_next = qof(t_next);
@@ -2121,6 +2158,10 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
                     if (ch < Cn) acc[ch] = fmaf(gch[ch], wn, acc[ch]);
             }
         }
+        // ---- the ticket for the group after this one: in flight during the epilogue ---------------------------
+        uint32_t ticket = 0;
+        if (CL && claiming && lane == 0)
+            ticket = __hip_atomic_fetch_add(claim_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // ---- per-task reductions, clip, stores -------------------------------------------------------------
         if (PH != 1) {
             gx = task_sum<RP>(gx, grp);
@@ -2174,6 +2215,13 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
                 for (int ch = 0; ch < CM; ++ch)
                     if (ch < Cn) grad_feat[(size_t)p * Cn + ch] = acc[ch];
             }
+        }
+        if (CL && claiming) {
+            const uint32_t q_claim = claim_base + claim_slot +
+                                     (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket) * FB_CLAIM_CTRS;
+            if (q_claim >= n_groups) break;   // the round is handed out: leave (no waiting)
+            p_nx = task_ids(q_claim);
+            continue;
         }
         if (!more) break;
         t_cur = t_next;
@@ -2245,7 +2293,7 @@ using namespace dss;
 
 // Workspace of the two-launch preparation (P <= PREP_MAX_POINTS), relative to its own base.
 struct PrepLayout {
-    size_t seg_count, vis_list, vis_keys, chunk_hist, seg_range, rs, alpha, tags, bytes;
+    size_t seg_count, vis_list, vis_keys, chunk_hist, seg_range, rs, alpha, tags, claim, bytes;
     int chunks, per;  // segments, points per thread of the compaction kernel (segment = per * 1024 points)
     int f_chunks, f_per;  // two-launch backward (fb_prep_segment): segments of f_per * 256 points, at most 64 (whole image:
                           // the gather maps a task to its segment with one ballot over 64 lanes) or FB_MAX_SEG (row band: the
@@ -2270,6 +2318,7 @@ static PrepLayout prep_layout(int N, int64_t P, int S, bool band = false)
     L.chunk_hist = off; off += align_up(n * (size_t)FB_MAX_SEG * 256 * 4, 256);   // (any segmentation: <= FB_MAX_SEG segments)
     L.seg_range = off;  off += align_up(n * (size_t)FB_MAX_SEG * 8, 256);
     L.tags = off;       off += align_up((size_t)FB_TAGS * 8, 256);   // rs tags of the fused gather launch
+    L.claim = off;      off += align_up((size_t)FB_CLAIM_WORDS * 4, 256);   // claim counters of the fused gather launch
     L.rs = off;         off += align_up(n * 4, 256);
     L.alpha = off;      off += align_up(n * (size_t)(S > 0 ? S : 0) * (size_t)(S > 0 ? S : 0) * 4, 256);  // S = 0: none
     L.bytes = off;
@@ -2587,10 +2636,15 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
     // with resident(v) = n_cus x the workgroups of v resident per CU.
     const unsigned cap = (unsigned)n_cus * resident_blocks(dev, (const void *)gather_kernel({C == 3, true, 4, true, false, false, false}), 256);
     const unsigned pgrid = (unsigned)((P + 3) / 4 < cap ? (P + 3) / 4 : cap);
+    const int grid_opt = option(DSS_OPT_BACKWARD_GRID);
     auto gather_grid = [&](const GatherVariant &v, bool fused_launch) -> unsigned {
-        if (fused_launch && !v.prep) return pgrid;
-        const unsigned g = std::min(pgrid, (unsigned)n_cus * resident_blocks(dev, (const void *)gather_kernel(v), 256));
-        return v.prep ? std::max(g, (unsigned)N + 8u) : g;
+        if (fused_launch && !v.prep) return grid_opt > 0 ? std::min(pgrid, std::max((unsigned)grid_opt, (unsigned)N + 8u)) : pgrid;
+        unsigned g = std::min(pgrid, (unsigned)n_cus * resident_blocks(dev, (const void *)gather_kernel(v), 256));
+        if (v.prep) g = std::max(g, (unsigned)N + 8u);
+        // DSS_OPT_BACKWARD_GRID: a cap on the persistent grid, within [N + 8, automatic] (tests reach every dealing case of
+        // the gather with a few thousand points through it; A/B measurements probe grid sizes)
+        if (grid_opt > 0) g = std::min(g, std::max((unsigned)grid_opt, (unsigned)N + 8u));
+        return g;
     };
     const uint32_t large_waves = 6u * (uint32_t)n_cus * 4u;
     // tasks per wavefront: four when the list is long enough to keep every resident wavefront busy with whole groups
@@ -2656,6 +2710,7 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
         FP.chunk_hist = reinterpret_cast<uint32_t *>(w + L.chunk_hist);
         FP.seg_range = reinterpret_cast<uint2 *>(w + L.seg_range);
         FP.tags = reinterpret_cast<unsigned long long *>(w + L.tags);
+        FP.claim = reinterpret_cast<uint32_t *>(w + L.claim);
         FP.rs = rs; FP.P = P;
         FP.chunks = L.f_chunks; FP.per = L.f_per; FP.radii_s = radii_s;
         float *plane = reinterpret_cast<float *>(w + L.alpha);

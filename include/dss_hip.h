@@ -81,13 +81,19 @@ DSS_API const char *dss_last_error(void);
  *                             5 = three (segments + alpha plane | medians | gather); any other value (1, 3, ...) = the
  *                             round-3 sequence (compaction | median | gather kernels).  4 and 5 use the bucket-sorted median
  *                             of raster_backward.hip.  Results do not depend on it.
+ *   DSS_OPT_BACKWARD_GRID   cap on the persistent grid of the backward gather, in workgroups: 0 (default) = automatic (one
+ *                             workgroup per four points, at most what stays resident); a positive value is clamped to
+ *                             [N + 8, automatic].  Exists so that a test can reach every dealing case of the gather (full
+ *                             rounds, a claimed last round) with a few thousand points, and for A/B measurements of grid
+ *                             sizes.  Results do not depend on it.
  * Returns DSS_ERR_INVALID_ARGUMENT for an unknown option or value. */
 #define DSS_OPT_LEAN_WORKSPACE 0
 #define DSS_OPT_BACKWARD_TPW 1
 #define DSS_OPT_BACKWARD_ADDR64 2
 #define DSS_OPT_BACKWARD_FUSED 3
 #define DSS_OPT_KNN_QUERY 4
-#define DSS_OPT_COUNT 5
+#define DSS_OPT_BACKWARD_GRID 5
+#define DSS_OPT_COUNT 6
 DSS_API int dss_band_rows(int row0, int row1, int row_cycle); /* rows of a band tensor (see `row_cycle` above) */
 DSS_API int dss_set_option(int option, int value);
 DSS_API int dss_get_option(int option);

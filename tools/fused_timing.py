@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): per-workgroup phase stamps (100 MHz s_memrealtime) inside the single-launch backward
 (render_backward_kernel<..., PREP>): when the segment / median workgroups finish, when the waiters are released, when the
-launch ends.   python tools/fused_timing.py [mode 2|3]"""
+launch ends.   python tools/fused_timing.py [mode 4] [prebuilt timing library]
+(without a library the timing build -DDSS_FINE_TIMING is compiled here, next to the tool's other output)"""
 import ctypes, os, subprocess, sys
 import numpy as np
 import torch
@@ -9,11 +10,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 out_dir = os.path.join(ROOT, "gpurun_out"); os.makedirs(out_dir, exist_ok=True)
 so = os.path.join(out_dir, "libdss_hip_timing.so"); src = os.path.join(ROOT, "dss_amd", "csrc")
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                "-fno-fast-math", "-fvisibility=hidden", "-DDSS_FINE_TIMING",
-                *[os.path.join(src, f) for f in ("api.hip", "raster_forward.hip", "raster_backward.hip", "blend.hip", "setup.hip",
-                                                  "knn.hip", "shading.hip", "regularizers.hip", "image_loss.hip")],
-                "-o", so], check=True)
+if len(sys.argv) > 2:
+    so = os.path.abspath(sys.argv[2])
+else:
+    import glob
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
+                    "-fno-fast-math", "-fvisibility=hidden", "-DDSS_FINE_TIMING", *sorted(glob.glob(os.path.join(src, "*.hip"))),
+                    "-o", so], check=True)
 from dss_amd import _lib, ops
 _lib.LIB_PATH = so
 import bench
