@@ -442,8 +442,11 @@ def test_project_backward_fused_clip_equals_clip_then_project():
 @pytest.mark.parametrize("N", [1, 3, 8, 11])
 def test_project_backward_reduces_the_feature_gradients_of_a_shared_cloud(N):
     """`dss_project_backward_features`: the per-camera feature gradients of a cloud shared by N cameras summed over the
-    cameras in the launch that projects the position gradients (more than eight cameras take a second batch of loads);
-    the position gradients are those of dss_project_backward bit for bit, with and without the clip."""
+    cameras in the launch that projects the position gradients; the position gradients are those of dss_project_backward
+    bit for bit, with and without the clip.  At Pw = 3001 every N >= 2 here runs `project_backward_shared_kernel` (eight
+    lanes per point): N = 11 is the second trip of its lanes 0 ... 2, not the second batch of eight cameras of the one-thread
+    `project_backward_kernel`.  That batch (Pw > 262,144) is run, and pinned to fp64 entry by entry, by
+    test_gpu_projection_grad.py::test_cases_against_the_closed_form[big9-*] / [big11-*] and ::test_both_sides_of_the_dispatch."""
     pts = scenes.normalize_unit_sphere(scenes.load_cloud("bunny")[0])[:3001]
     Pc = pts.shape[0]
     mats = [scenes.camera_matrices(2.0, 20.0, 360.0 * k / N + 10.0) for k in range(N)]
