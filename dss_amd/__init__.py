@@ -36,12 +36,13 @@ def calling_thread_backward():
         torch.autograd.set_multithreading_enabled(was)
 
 
-_CLOUD_OPS = ("upsample", "upsample_clouds", "remove_outliers", "denoise_normals", "project_to_latent_surface")
+_CLOUD_OPS = ("upsample", "upsample_clouds", "remove_outliers", "denoise_normals", "project_to_latent_surface",
+              "sample_farthest_points", "subsample")
 
 
 def __getattr__(name):
     """``dss_amd.upsample`` / ``upsample_clouds`` / ``remove_outliers`` / ``denoise_normals`` / ``project_to_latent_surface``
-    (dss_amd/cloud_ops.py), imported on first use so that
+    / ``sample_farthest_points`` / ``subsample`` (dss_amd/cloud_ops.py), imported on first use so that
     ``import dss_amd`` itself stays free of torch."""
     if name in _CLOUD_OPS:
         from . import cloud_ops

@@ -6,7 +6,10 @@ search and the assembly of the grown cloud are the HIP kernels of ``dss_amd/csrc
 `denoise_normals` filters the normals over a neighbourhood (:515-552) and `project_to_latent_surface` moves every point
 onto a locally fitted implicit surface (RIMLS, :442-513); their kernels are ``dss_amd/csrc/smoothing.hip``, their contract
 is DESIGN 4.15.  Nothing here is differentiable: the reference uses these tools to re-parametrise a model between optimiser
-phases.
+phases.  The one that THINS a cloud evenly: `sample_farthest_points` (pytorch3d's call) and `subsample` pick a subset by
+farthest point sampling -- every new point the one farthest from those already picked, ties to the smallest id, no point
+picked twice -- in one persistent workgroup per cloud (``dss_amd/csrc/sampling.hip``); `subsample` with
+``method="random"`` is the reference's `subsample_randomly` (:260-279), which keeps the density of its input.
 """
 from typing import List, Optional, Sequence, Union
 
@@ -330,3 +333,125 @@ def _pad_to(packed, sizes, P: int):
         out[n, :s] = packed[f:f + s]
         f += s
     return out
+
+
+def _host_floats(x, N: int, name: str) -> List[float]:
+    """`_host_ints` for floats."""
+    if isinstance(x, torch.Tensor):
+        x = x.reshape(-1).tolist()
+    if isinstance(x, (int, float)):
+        x = [x] * N
+    x = [float(v) for v in x]
+    if len(x) == 1 and N > 1:
+        x = x * N
+    if len(x) != N:
+        raise ValueError("%s must be one number or %d of them, got %d" % (name, N, len(x)))
+    return x
+
+
+def check_sampling(who: str, sizes: Sequence[int], counts: Sequence[int], starts: Sequence[int]) -> None:
+    """The refusals of the sampling calls, from host integers, before anything is launched (ValueError)."""
+    for n, (s, k, c) in enumerate(zip(sizes, counts, starts)):
+        if k < 0:
+            raise ValueError("%s: cloud %d is asked for %d samples, a negative count" % (who, n, k))
+        if c < 0 or c >= max(s, 1):
+            raise ValueError("%s: start_idx %d lies outside cloud %d of %d points" % (who, c, n, s))
+
+
+def _require_gpu_cloud(t) -> None:
+    if not t.is_cuda:
+        raise RuntimeError("dss_amd: points is on %s; the HIP path needs GPU tensors (no CPU fallback)" % t.device)
+
+
+@torch.no_grad()
+def sample_farthest_points(points, lengths=None, K: Union[int, Sequence[int], torch.Tensor] = 50,
+                           start_idx: Union[int, Sequence[int], torch.Tensor] = 0):
+    """Farthest point sampling of every cloud, pytorch3d's ``sample_farthest_points`` with a fixed start ->
+    ``(selected (N, K_max, 3), idx (N, K_max) int64)``, K_max = max(K): the points of every cloud that were picked, in the
+    order of picking, and their cloud-local ids.  Behind the min(K_n, P_n) samples of cloud n: id -1, point 0
+    (pytorch3d's padding).
+
+    points (N,P,3) padded with ``lengths`` the N sizes (None: all P), or a ``PointClouds3D`` (its own sizes).  ``K`` and
+    ``start_idx`` are one integer or N of them; cloud n starts at its point ``start_idx[n]``.
+
+    The selection: with d[i] the squared distance, in fp32 as ``(dx dx + dy dy) + dz dz``, of point i to the
+    nearest point picked so far, the next pick is the point of the largest d, among equals the one of the SMALLEST id, and
+    a picked point is never picked again -- so K_n = P_n returns a permutation even when points coincide.  Those are the
+    two places where this departs from pytorch3d, which lets its argmax break ties and repeats a point once all distances
+    are 0.  A point with a NaN coordinate keeps d = +inf: it is picked second and then never again.  Every cloud is sampled
+    as if it were alone, by one persistent workgroup; padding rows are not read.
+
+    Not differentiable.  With integers given as Python integers the call reads nothing back from the device and can be
+    captured in a graph; integers given as GPU tensors cost one read each.  Raises ValueError, before anything is launched,
+    for wrong shapes, a negative count and a ``start_idx`` outside its cloud.  GPU tensors only: no CPU fallback."""
+    who = "sample_farthest_points"
+    if isinstance(points, PointClouds3D):
+        sizes = [int(p.shape[0]) for p in points.points_list()]
+        N, firsts = len(sizes), [sum(sizes[:n]) for n in range(len(sizes))]
+        packed = points.points_packed().detach()
+    else:
+        if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3:
+            raise ValueError("%s expects padded points (N,P,3) or a PointClouds3D" % who)
+        N, P = points.shape[0], points.shape[1]
+        sizes = _host_ints(P if lengths is None else lengths, N, "lengths")
+        if any(s < 0 or s > P for s in sizes):
+            raise ValueError("lengths must lie in 0 .. P = %d" % P)
+        firsts = [n * P for n in range(N)]   # the padded batch IS a packed array with rows that no cloud owns
+        packed = points.detach().reshape(N * P, 3)
+    counts, starts = _host_ints(K, N, "K"), _host_ints(start_idx, N, "start_idx")
+    check_sampling(who, sizes, counts, starts)
+    _require_gpu_cloud(packed)
+    dev, K_max = packed.device, max(counts)
+    first = _device_ints(firsts, dev)
+    idx = ops.farthest_points(packed.to(torch.float32), first, _device_ints(sizes, dev), _device_ints(counts, dev),
+                              _device_ints(starts, dev) if any(starts) else None, K_max)
+    if packed.shape[0] == 0 or K_max == 0:
+        return packed.new_zeros((N, K_max, 3)), idx
+    selected = packed[(first[:, None] + idx.clamp(min=0)).clamp(max=packed.shape[0] - 1)]   # (a padding id reads any row)
+    return torch.where((idx >= 0)[..., None], selected, torch.zeros_like(selected)), idx
+
+
+@torch.no_grad()
+def subsample(point_clouds, n_points: Union[None, int, Sequence[int], torch.Tensor] = None,
+              ratio: Union[None, float, Sequence[float], torch.Tensor] = None, method: str = "farthest",
+              start_idx: Union[int, Sequence[int], torch.Tensor] = 0, generator=None) -> PointClouds3D:
+    """Thin every cloud of a ``PointClouds3D`` to ``n_points`` points (at most its size) or to ``int(ratio * P_n)`` of
+    them -> a new container (detached tensors; the input is not modified).  Normals and features follow their points; the
+    rows stand in the order in which they were picked.  Exactly one of ``n_points`` / ``ratio`` (one value or one per cloud).
+
+    ``method="farthest"``: an even subset by farthest point sampling from ``start_idx`` (`sample_farthest_points`: ties to
+    the smallest id, no point twice), the inverse of `upsample`.  GPU tensors only.
+    ``method="random"``: the reference's `subsample_randomly` (DSS/core/cloud.py:260-279), the first rows of a
+    ``torch.randperm(P_n)`` drawn on the cloud's device from ``generator``; it keeps the density of the input.
+
+    Not differentiable.  Raises ValueError, before anything is launched, for a negative count, a ``ratio`` outside [0, 1],
+    a ``start_idx`` outside its cloud, both or neither of ``n_points`` / ``ratio`` and an unknown ``method``."""
+    if method not in ("farthest", "random"):
+        raise ValueError("subsample: method must be 'farthest' or 'random', got %r" % (method,))
+    if (n_points is None) == (ratio is None):
+        raise ValueError("subsample: give exactly one of n_points and ratio")
+    pts = point_clouds.points_list()
+    N = len(pts)
+    sizes = [int(p.shape[0]) for p in pts]
+    if ratio is not None:
+        ratios = _host_floats(ratio, N, "ratio")
+        if any(not 0.0 <= r <= 1.0 for r in ratios):
+            raise ValueError("subsample: ratio must lie in [0, 1], got %r" % (ratio,))
+        counts = [int(r * s) for r, s in zip(ratios, sizes)]
+    else:
+        counts = _host_ints(n_points, N, "n_points")
+    starts = _host_ints(start_idx, N, "start_idx") if method == "farthest" else [0] * N
+    check_sampling("subsample", sizes, counts, starts)
+    counts = [min(k, s) for k, s in zip(counts, sizes)]
+    dev = pts[0].device
+    if method == "farthest":
+        _require_gpu_cloud(pts[0])
+        first, num = _ranges(sizes, dev)
+        packed = torch.cat([p.detach().to(torch.float32) for p in pts], dim=0).contiguous()
+        idx = ops.farthest_points(packed, first, num, _device_ints(counts, dev),
+                                  _device_ints(starts, dev) if any(starts) else None, max(counts))
+        keep = [idx[n, :k] for n, k in enumerate(counts)]
+    else:
+        keep = [torch.randperm(s, device=dev, generator=generator)[:k] for s, k in zip(sizes, counts)]
+    pick = lambda lst: None if lst is None else [t.detach().index_select(0, k) for t, k in zip(lst, keep)]
+    return PointClouds3D(pick(pts), pick(point_clouds.normals_list()), pick(point_clouds.features_list()))

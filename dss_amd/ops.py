@@ -1373,3 +1373,6 @@ from .upsample_ops import upsample_candidates, upsample_insert  # noqa: E402,F40
 # and the two kernels that clean a cloud (smoothing_ops.py; the public calls are dss_amd.cloud_ops.denoise_normals and
 # project_to_latent_surface)
 from .smoothing_ops import denoise_normals, rimls_step  # noqa: E402,F401
+# and the kernel that thins a cloud evenly (sampling_ops.py; the public calls are dss_amd.cloud_ops.sample_farthest_points
+# and subsample)
+from .sampling_ops import farthest_points  # noqa: E402,F401

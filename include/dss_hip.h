@@ -670,6 +670,41 @@ DSS_API int dss_rimls_step(const float *points_in /* (P,3) */, const float *norm
                            float *points_out /* (P,3) */, uint8_t *live_out /* (P,) */, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Thinning a cloud evenly: farthest point sampling of every cloud of a packed batch.  The reference has only the random
+ * `subsample_randomly` (DSS/core/cloud.py:260-279), which keeps the density of its input, and leaves the process for
+ * MeshLab's Poisson-disk filter where it wants an even sample (DSS/utils/dataset.py:118-127).
+ * For cloud n with P_n = num_pts[n] points (packed rows first_idx[n] .. + P_n), k_n = min(n_samples[n], P_n) and a start
+ * id s_n = start[n] in [0, P_n) (start == NULL: 0):
+ *   d[i] = +inf for every point, c_0 = s_n, r_0 = +inf.
+ *   Step t = 0 .. k_n - 1: emit idx[n][t] = c_t (cloud-local id) and sel_sqdist[n][t] = r_t, then for every i
+ *     dist = (dx dx + dy dy) + dz dz, dx = x_i - x_c   (fp32, every operation rounded on its own)
+ *     d[i] = dist < d[i] ? dist : d[i]                  (a NaN distance never changes d)
+ *     d[c_t] = -1 after the update                      (a selected point is never selected again)
+ *     c_{t+1} = the i with the largest d[i], ties to the SMALLEST id; r_{t+1} = that d.
+ *   Entries t >= k_n of a row: idx = -1, sel_sqdist = 0.
+ * So r_1 >= r_2 >= ..., the ids of a row are distinct, and k_n = P_n yields a permutation even with duplicate points.
+ * Two deviations from pytorch3d's `sample_farthest_points`: there a selected point keeps its distance 0 and is selected
+ * again once every distance is 0 (duplicate points), and ties go to whatever its argmax returns.
+ * Every slot of both outputs is written by every call that launches; a repeated call returns the same bits.  Every cloud is
+ * sampled as if it were alone; rows of the packed array that no cloud owns are never read; an empty cloud gives a row of
+ * -1.  n_samples[n] above K_max is clamped to K_max, a start[n] outside the cloud is clamped into it, a range that leaves
+ * the packed array is cut to it: the kernels follow no id that leaves its cloud.
+ * One workgroup per cloud for all of its steps (the chain of dependent steps is the whole cost): no atomics, no workgroup
+ * waits for another, one barrier per selected point.  Clouds of at most 24,576 points stay in registers; larger ones keep d
+ * in `workspace` (dss_farthest_points_workspace bytes: 0 when P <= 24,576) and re-read their points in every step.  The
+ * path is chosen per workgroup on the device from num_pts[n]; nothing is read back.
+ * Refusals (DSS_ERR_INVALID_ARGUMENT, nothing launched): N < 1, P < 0 or P >= 2^31, K_max < 0; a NULL pointer other than
+ * start / sel_sqdist (and workspace when the query says 0); a workspace smaller than the query says.  P == 0 or K_max == 0
+ * returns 0 without a launch (and writes nothing).
+ * ------------------------------------------------------------------------------------------- */
+DSS_API size_t dss_farthest_points_workspace(int N, int64_t P);
+DSS_API int dss_farthest_points(const float *points /* (P,3) */, const int64_t *first_idx, const int64_t *num_pts,
+                                const int64_t *n_samples /* (N,) */, const int64_t *start /* (N,) or NULL = 0 */,
+                                int N, int64_t P, int64_t K_max, int64_t *idx /* (N,K_max) */,
+                                float *sel_sqdist /* (N,K_max) or NULL */, void *workspace, size_t workspace_bytes,
+                                void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Phong shading of the points = LightingTexture.forward (DSS/core/texture.py:65-125):
  * apply_lighting (:26-63) with lighting.py:10-77 (diffuse) and :80-172 (specular) for L PointLights
  * (point_lights = 1: light_vec = location, direction = location - point, lighting.py:239-302) or
