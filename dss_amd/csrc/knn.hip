@@ -9,13 +9,25 @@
 // res^3 grid, then one thread per point visits Chebyshev rings of cells until the K-th distance found
 // is provably final (<= distance to the unvisited region).
 //
-//   knn_bbox      per-cloud bounding box (ordered-int atomics)
-//   knn_count     cell of every point, per-cell counts
-//   knn_scan      exclusive scan of the cell counts: 1024-cell blocks scanned locally, then offset by the block prefix
-//   knn_fill      counting sort: points grouped by cell
-//   knn_query     ring search, K smallest squared distances in registers; one thread per point IN CELL ORDER, so the
-//                 lanes of a wavefront walk the same few cells (same trip counts, broadcast loads)
-//   cloud_mean    deterministic per-cloud mean * scale, clamped (the global-h statistic)
+// The kernels, and the chains of launches (host section below) that use them:
+//   small build (build_grid: P <= KNN_SMALL_P, at most KNN_GRID_LDS clouds and KNN_SCAN1_BLOCKS scan blocks)
+//       knn_bbox_partial (also zeroes the counts), knn_count_grid, knn_scan_single, knn_fill
+//   eight-launch build (build_grid, otherwise)
+//       memset of the counts, knn_init, knn_bbox, knn_grid, knn_count, knn_scan_local, knn_scan_add, knn_fill
+//   skip structure of clustered clouds (build_skip_structure, P >= KNN_SKIP_MIN_P)
+//       knn_dense_list, knn_subsort, knn_block_box
+//   the two queries (query_plain, query_per_camera): K smallest squared distances in registers, IN CELL ORDER, so the
+//   lanes of a wavefront walk the same few cells
+//       knn_query        one thread per point
+//       knn_query_coop   KNN_LPQ lanes per point
+//   per-camera rows (dss_knn_kth_sqdist_view): knn_fill raises the "camera drops points" flags, the VIEW instantiations
+//   of the two queries search among the kept points, knn_view_rows copies the row of a camera that drops nothing
+//   statistics: cloud_mean (the global-h statistic), renderable_sum + renderable_mean (the same under depth culling)
+//   another cloud's nearest point and the chamfer gradient (end of the file): nearest_query, chamfer_backward
+// The rules that several of them share are device functions, each stated once: knn_box_reduce (box of a cloud),
+// knn_make_grid (grid from a box), knn_cell_coords / knn_cell_of (cell of a position), wave_incl_scan / wave_xor_sum /
+// block_excl_scan (scans and sums), KnnCamera (depth test of a camera), knn_insert (K-best list), knn_ring_bound /
+// knn_search_done (when a ring search is final), knn_kth_of / knn_write_result (what a query reports).
 #include "common.h"
 
 namespace dss {
@@ -30,18 +42,37 @@ struct KnnGrid {  // per cloud, device resident (8 floats)
     int pad0, pad1;
 };
 
-// Bounding box per cloud.  Grid (G, N): workgroups of cloud n stride over its points, reduce min/max in
-// registers -> wave (shuffles) -> workgroup (LDS) -> one atomic per bound and WORKGROUP.  (One atomic set per POINT,
-// the first version, serialised P same-address atomics: 2.2 ms at 80k points.)
-__global__ __launch_bounds__(256) void knn_bbox_kernel(const float *__restrict__ pts, const int64_t *__restrict__ first_idx,
-                                                       const int64_t *__restrict__ num_pts, int N, int64_t P,
-                                                       int *__restrict__ bbox /* (N,6) ordered ints */)
+// Sum over the wavefront by xor butterfly, offsets 32 down to 1: every lane ends with the total.  (The float and double
+// sums of the statistics are pinned to this order; common.h's wave_sum adds in another one.)
+template <typename T>
+__device__ __forceinline__ T wave_xor_sum(T v)
 {
-    const int n = blockIdx.y;
-    const int64_t f = first_idx[n], cnt = num_pts[n];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Inclusive scan over the wavefront: lane l ends with the sum of lanes 0..l.
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(v, o);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// Box of the points f + i0, f + i0 + step, ... of a cloud (f, cnt), reduced over a 256-thread workgroup: registers ->
+// wave (shuffles) -> workgroup (LDS).  Threads 0..5 return the workgroup's value d = threadIdx.x as an ordered int (0..2:
+// min x y z, 3..5: max), +inf / -inf in that space when the workgroup saw no point; NaN positions are passed over.
+__device__ __forceinline__ int knn_box_reduce(const float *__restrict__ pts, int64_t f, int64_t cnt, int64_t P, int64_t i0,
+                                              int64_t step, int (&part)[4][6] /* LDS */)
+{
     int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
     int hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = i0; i < cnt; i += step) {
         const int64_t p = f + i;
         if (p >= P) break;
         const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
@@ -57,21 +88,35 @@ __global__ __launch_bounds__(256) void knn_bbox_kernel(const float *__restrict__
             lo[d] = min(lo[d], __shfl_xor(lo[d], o));
             hi[d] = max(hi[d], __shfl_xor(hi[d], o));
         }
-    __shared__ int part[4][6];
     const int wid = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) { part[wid][d] = lo[d]; part[wid][3 + d] = hi[d]; }
     }
     __syncthreads();
-    if (threadIdx.x < 6) {  // one atomic per workgroup and bound
+    int v = 0;
+    if (threadIdx.x < 6) {
         const int d = threadIdx.x;
-        int v = part[0][d];
+        v = part[0][d];
 #pragma unroll
         for (int w = 1; w < 4; ++w) v = d < 3 ? min(v, part[w][d]) : max(v, part[w][d]);
-        if (d < 3 && v != 0x7fffffff) atomicMin(&bbox[6 * n + d], v);
-        if (d >= 3 && v != (int)0x80000000) atomicMax(&bbox[6 * n + d], v);
     }
+    return v;
+}
+
+// Bounding box per cloud.  Grid (G, N): workgroups of cloud n stride over its points and reduce them (knn_box_reduce) ->
+// one atomic per bound and WORKGROUP.  (One atomic set per POINT, the first version, serialised P same-address atomics:
+// 2.2 ms at 80k points.)
+__global__ __launch_bounds__(256) void knn_bbox_kernel(const float *__restrict__ pts, const int64_t *__restrict__ first_idx,
+                                                       const int64_t *__restrict__ num_pts, int N, int64_t P,
+                                                       int *__restrict__ bbox /* (N,6) ordered ints */)
+{
+    __shared__ int part[4][6];
+    const int n = blockIdx.y, d = threadIdx.x;
+    const int v = knn_box_reduce(pts, first_idx[n], num_pts[n], P, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                                 (int64_t)gridDim.x * blockDim.x, part);
+    if (d < 3 && v != 0x7fffffff) atomicMin(&bbox[6 * n + d], v);   // (an untouched value stays out of the atomics)
+    if (d >= 3 && d < 6 && v != (int)0x80000000) atomicMax(&bbox[6 * n + d], v);
 }
 
 __global__ void knn_init_kernel(int N, int *__restrict__ bbox)
@@ -80,30 +125,54 @@ __global__ void knn_init_kernel(int N, int *__restrict__ bbox)
     if (i < 6 * N) bbox[i] = (i % 6 < 3) ? 0x7fffffff : (int)0x80000000;  // +inf / -inf in ordered-int space
 }
 
-__global__ void knn_grid_kernel(const int *__restrict__ bbox, const int64_t *__restrict__ num_pts, int N, int res_cap,
-                                KnnGrid *__restrict__ grids)
+// Grid of a cloud from its box (six ordered ints: min x y z, max x y z) and its point count.
+__device__ __forceinline__ KnnGrid knn_make_grid(const int (&box)[6], int64_t npts, int res_cap)
 {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
     KnnGrid g;
-    const float x0 = ord2f(bbox[6 * n]), y0 = ord2f(bbox[6 * n + 1]), z0 = ord2f(bbox[6 * n + 2]);
-    const float x1 = ord2f(bbox[6 * n + 3]), y1 = ord2f(bbox[6 * n + 4]), z1 = ord2f(bbox[6 * n + 5]);
+    const float x0 = ord2f(box[0]), y0 = ord2f(box[1]), z0 = ord2f(box[2]);
+    const float x1 = ord2f(box[3]), y1 = ord2f(box[4]), z1 = ord2f(box[5]);
     const float ext = fmaxf(fmaxf(x1 - x0, y1 - y0), fmaxf(z1 - z0, 1e-12f));
     // surface-like clouds occupy ~3 res^2 cells: aim at ~8 points per occupied cell
-    int res = (int)ceilf(sqrtf((float)num_pts[n] / 24.0f));
+    int res = (int)ceilf(sqrtf((float)npts / 24.0f));
     res = max(1, min(res_cap, res));  // res_cap: the resolution the workspace was sized for (knn_res_cap)
     g.minx = x0; g.miny = y0; g.minz = z0;
     g.cell = ext / (float)res * 1.0001f;
     g.inv_cell = 1.0f / g.cell;
     g.res = res;
     g.pad0 = g.pad1 = 0;
-    grids[n] = g;
+    return g;
+}
+
+__global__ void knn_grid_kernel(const int *__restrict__ bbox, const int64_t *__restrict__ num_pts, int N, int res_cap,
+                                KnnGrid *__restrict__ grids)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    int box[6];
+#pragma unroll
+    for (int d = 0; d < 6; ++d) box[d] = bbox[6 * n + d];
+    grids[n] = knn_make_grid(box, num_pts[n], res_cap);
 }
 
 __device__ __forceinline__ int cell_coord(float v, float mn, float inv_cell, int res)
 {
     const int c = (int)floorf((v - mn) * inv_cell);
     return min(max(c, 0), res - 1);
+}
+// Cell of a position in a cloud's grid: its three coordinates, and its linear index (cells consecutive along x are
+// consecutive in memory).
+// (returned by value: coordinates handed back through references stay memory until the call is inlined, and the ring
+// walk's tests on them compile to branches where they were mask arithmetic -- 1 to 3 % of a one-thread query call)
+__device__ __forceinline__ int3 knn_cell_coords(const KnnGrid &g, float x, float y, float z)
+{
+    return make_int3(cell_coord(x, g.minx, g.inv_cell, g.res), cell_coord(y, g.miny, g.inv_cell, g.res),
+                     cell_coord(z, g.minz, g.inv_cell, g.res));
+}
+__device__ __forceinline__ int knn_cell_index(const KnnGrid &g, int cx, int cy, int cz) { return (cz * g.res + cy) * g.res + cx; }
+__device__ __forceinline__ int knn_cell_of(const KnnGrid &g, float x, float y, float z)
+{
+    const int3 c = knn_cell_coords(g, x, y, z);
+    return knn_cell_index(g, c.x, c.y, c.z);
 }
 
 __global__ __launch_bounds__(256) void knn_count_kernel(const float *__restrict__ pts, const int64_t *__restrict__ first_idx,
@@ -117,10 +186,7 @@ __global__ __launch_bounds__(256) void knn_count_kernel(const float *__restrict_
     const int n = find_cloud(p, first_idx, num_pts, N);
     if (n < 0) { cell_of[p] = -1; return; }
     const KnnGrid g = grids[n];
-    const int cx = cell_coord(pts[3 * p], g.minx, g.inv_cell, g.res);
-    const int cy = cell_coord(pts[3 * p + 1], g.miny, g.inv_cell, g.res);
-    const int cz = cell_coord(pts[3 * p + 2], g.minz, g.inv_cell, g.res);
-    const int c = (cz * g.res + cy) * g.res + cx;
+    const int c = knn_cell_of(g, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]);
     cell_of[p] = c;
     // the counting atomic's return value is the point's slot inside the cell: the fill pass needs no second atomic (on a
     // clustered cloud both passes are bound by the fullest cell: 3,900 same-address atomics, 86 us each way)
@@ -131,21 +197,18 @@ __global__ __launch_bounds__(256) void knn_count_kernel(const float *__restrict_
 // Pass 1: local exclusive scan -> offsets, block total -> blk_tot.  Pass 2: every block sums the totals of the blocks
 // before it (at most 2048 values) and adds that prefix; the block holding the last cell also writes the end sentinel.
 // (The first version scanned all res^3 cells with ONE workgroup per cloud: 288 us at res = 64.)
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *wave_tot /* LDS [4] */, uint32_t &total)
+// Exclusive scan over a workgroup of WAVES wavefronts (one barrier); `total` = the sum over the workgroup.
+template <int WAVES>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wave_tot /* LDS [WAVES] */, uint32_t &total)
 {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
+    const uint32_t incl = wave_incl_scan(v);
     if (lane == 63) wave_tot[wid] = incl;
     __syncthreads();
     uint32_t before = 0;
     total = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
+    for (int w = 0; w < WAVES; ++w) {
         const uint32_t t = wave_tot[w];
         before += (w < wid) ? t : 0u;
         total += t;
@@ -168,7 +231,7 @@ __global__ __launch_bounds__(256) void knn_scan_local_kernel(const uint32_t *__r
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = (c0 + i < cells) ? counts[base + c0 + i] : 0u;
     uint32_t total;
-    uint32_t run = block_excl_scan_256(v[0] + v[1] + v[2] + v[3], wave_tot, total);
+    uint32_t run = block_excl_scan<4>(v[0] + v[1] + v[2] + v[3], wave_tot, total);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (c0 + i < cells) offsets[base + c0 + i] = run;
@@ -190,7 +253,7 @@ __global__ __launch_bounds__(256) void knn_scan_add_kernel(const KnnGrid *__rest
     uint32_t part = 0;
     for (int i = tid; i < b; i += 256) part += blk_tot[(size_t)n * nblk_max + i];
     uint32_t prefix;
-    block_excl_scan_256(part, wave_tot, prefix);  // only the total is needed: blocks before b
+    block_excl_scan<4>(part, wave_tot, prefix);  // only the total is needed: blocks before b
     const int c0 = b * KNN_SCAN_BLOCK + 4 * tid;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -213,6 +276,22 @@ struct KnnView {
     uint32_t *culls;       // (cameras) != 0: the camera drops at least one point of its cloud (written by knn_fill_kernel)
     int n_cams;
 };
+// What the depth test needs of a camera: the depth column of its view matrix and its two planes.  kept() is the test of
+// setup_point_compute, same expression.
+struct KnnCamera {
+    float v2, v6, v10, v14, zn, zf;
+    __device__ __forceinline__ static KnnCamera load(const float *V, const float *znear, const float *zfar, int cam)
+    {
+        const float *vm = V + 16 * cam;
+        return {vm[2], vm[6], vm[10], vm[14], znear[cam], zfar[cam]};
+    }
+    __device__ __forceinline__ float depth(float x, float y, float z) const { return x * v2 + y * v6 + z * v10 + 1.0f * v14; }
+    __device__ __forceinline__ bool kept(float x, float y, float z) const
+    {
+        const float zview = depth(x, y, z);
+        return (zview >= zn) && (zview <= zf);
+    }
+};
 // The unmasked search of the whole cloud runs FIRST (one launch: statistic and K-th distance of every point); a camera's
 // masked search is only needed for a query that has a dropped point among the neighbours that count, and a dropped point
 // lies on the far side of one of the camera's two depth planes: the distance from a KEPT query to it is at least the
@@ -226,14 +305,14 @@ struct KnnView {
 // masked list is the unmasked list; with rho = r < the K-th distance, the entries within r are the same in both lists and
 // the others do not count.  The margin allows for the rounding of the view depth (1e-5 (1 + |z|)) and for a view matrix
 // whose depth axis is not a unit vector.  plain_dk = inf (fewer than K points in the cloud) never takes the shortcut.
-__device__ __forceinline__ bool knn_view_shortcut(uint32_t camera_drops, float x, float y, float z, float v2, float v6, float v10,
-                                                  float v14, float zn, float zf, float plain_dk, float r2)
+__device__ __forceinline__ bool knn_view_shortcut(uint32_t camera_drops, float x, float y, float z, const KnnCamera &c,
+                                                  float plain_dk, float r2)
 {
     if (camera_drops == 0u) return true;
-    const float zview = x * v2 + y * v6 + z * v10 + 1.0f * v14;
-    const float margin = fminf(zview - zn, zf - zview) - 1e-5f * (1.0f + fabsf(zview));
+    const float zview = c.depth(x, y, z);
+    const float margin = fminf(zview - c.zn, c.zf - zview) - 1e-5f * (1.0f + fabsf(zview));
     const float rho2 = r2 > 0.0f ? fminf(plain_dk, r2) : plain_dk;
-    return margin > 0.0f && margin * margin > rho2 * (v2 * v2 + v6 * v6 + v10 * v10) * 1.0002f;
+    return margin > 0.0f && margin * margin > rho2 * (c.v2 * c.v2 + c.v6 * c.v6 + c.v10 * c.v10) * 1.0002f;
 }
 // mode 1 of dss_knn_kth_sqdist_view (one cloud, several cameras): the row of a camera that drops nothing is the unmasked search
 // itself -- a coalesced copy; the query launches skip such cameras
@@ -249,11 +328,6 @@ __global__ __launch_bounds__(256) void knn_view_rows_kernel(float *__restrict__ 
     } else {
         for (int64_t j = i; j < min(i + 4, P); ++j) row[j] = plain[j];
     }
-}
-__device__ __forceinline__ bool knn_kept(float x, float y, float z, float v2, float v6, float v10, float v14, float zn, float zf)
-{
-    const float zview = x * v2 + y * v6 + z * v10 + 1.0f * v14;   // the expression of setup_point_compute
-    return (zview >= zn) && (zview <= zf);
 }
 
 __global__ __launch_bounds__(256) void knn_fill_kernel(const float *__restrict__ pts, const int64_t *__restrict__ first_idx,
@@ -276,8 +350,7 @@ __global__ __launch_bounds__(256) void knn_fill_kernel(const float *__restrict__
         // which cameras drop a point of their cloud (dss_knn_kth_sqdist_view): one atomic per wavefront and camera that does
         const int c0 = view.mode == 1 ? 0 : n, c1 = view.mode == 1 ? view.n_cams : n + 1;
         for (int cam = c0; cam < c1; ++cam) {
-            const float *vm = view.V + 16 * cam;
-            const bool drop = !knn_kept(x, y, z, vm[2], vm[6], vm[10], vm[14], view.znear[cam], view.zfar[cam]);
+            const bool drop = !KnnCamera::load(view.V, view.znear, view.zfar, cam).kept(x, y, z);
             unsigned long long m = __ballot(drop);
             // (one atomic per wavefront and camera, and none once the flag is seen up: 12,000 atomics on eight words took 100 us
             // at 8 x 100k.)  mode 2: a wavefront that straddles a cloud boundary holds lanes of different cameras -- one leader
@@ -350,9 +423,7 @@ __global__ __launch_bounds__(256) void knn_dense_list_kernel(const KnnGrid *__re
     const unsigned long long m = __ballot(dense);
     if (m == 0ull) return;
     const int lane = threadIdx.x & 63, leader = __builtin_ctzll(m);
-    uint32_t pts_here = dense ? cnt : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) pts_here += (uint32_t)__shfl_xor((int)pts_here, o);
+    const uint32_t pts_here = wave_xor_sum(dense ? cnt : 0u);
     uint32_t base = 0;
     if (lane == leader) {
         base = atomicAdd(n_list, (uint32_t)__popcll(m));
@@ -473,42 +544,13 @@ __global__ __launch_bounds__(256) void knn_bbox_partial_kernel(const float *__re
         for (size_t i = (size_t)(blockIdx.x - KNN_BB_WGS) * 256 + threadIdx.x; i < stride; i += zw * 256) c[i] = 0u;
         return;
     }
-    const int64_t f = first_idx[n], cnt = num_pts[n];
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
-    int hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)KNN_BB_WGS * 256) {
-        const int64_t p = f + i;
-        if (p >= P) break;
-        const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
-        if (!(x == x && y == y && z == z)) continue;
-        const int ox = f2ord(x), oy = f2ord(y), oz = f2ord(z);
-        lo[0] = min(lo[0], ox); lo[1] = min(lo[1], oy); lo[2] = min(lo[2], oz);
-        hi[0] = max(hi[0], ox); hi[1] = max(hi[1], oy); hi[2] = max(hi[2], oz);
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[d] = min(lo[d], __shfl_xor(lo[d], o));
-            hi[d] = max(hi[d], __shfl_xor(hi[d], o));
-        }
     __shared__ int part[4][6];
-    const int wid = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { part[wid][d] = lo[d]; part[wid][3 + d] = hi[d]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int d = threadIdx.x;
-        int v = part[0][d];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) v = d < 3 ? min(v, part[w][d]) : max(v, part[w][d]);
-        partial[((size_t)n * KNN_BB_WGS + blockIdx.x) * 6 + d] = v;
-    }
+    const int v = knn_box_reduce(pts, first_idx[n], num_pts[n], P, (int64_t)blockIdx.x * 256 + threadIdx.x,
+                                 (int64_t)KNN_BB_WGS * 256, part);
+    if (threadIdx.x < 6) partial[((size_t)n * KNN_BB_WGS + blockIdx.x) * 6 + threadIdx.x] = v;
 }
 
-// grid parameters of cloud n from the partial boxes (the arithmetic of knn_grid_kernel)
+// grid parameters of cloud n from the partial boxes, reduced over the lanes of a wavefront
 __device__ __forceinline__ KnnGrid knn_grid_from_partials(const int *__restrict__ partial, int n, int64_t npts, int res_cap, int lane)
 {
     int v[6];
@@ -521,18 +563,7 @@ __device__ __forceinline__ KnnGrid knn_grid_from_partials(const int *__restrict_
             v[d] = d < 3 ? min(v[d], t) : max(v[d], t);
         }
     }
-    KnnGrid g;
-    const float x0 = ord2f(v[0]), y0 = ord2f(v[1]), z0 = ord2f(v[2]);
-    const float x1 = ord2f(v[3]), y1 = ord2f(v[4]), z1 = ord2f(v[5]);
-    const float ext = fmaxf(fmaxf(x1 - x0, y1 - y0), fmaxf(z1 - z0, 1e-12f));
-    int res = (int)ceilf(sqrtf((float)npts / 24.0f));
-    res = max(1, min(res_cap, res));
-    g.minx = x0; g.miny = y0; g.minz = z0;
-    g.cell = ext / (float)res * 1.0001f;
-    g.inv_cell = 1.0f / g.cell;
-    g.res = res;
-    g.pad0 = g.pad1 = 0;
-    return g;
+    return knn_make_grid(v, npts, res_cap);
 }
 
 // count with the grid derived in place: one workgroup handles 256 consecutive packed points, its first wavefront reduces
@@ -561,10 +592,7 @@ __global__ __launch_bounds__(256) void knn_count_grid_kernel(const float *__rest
     const int n = find_cloud(p, first_idx, num_pts, N);
     if (n < 0) { cell_of[p] = -1; return; }
     const KnnGrid g = s_g[n];
-    const int cx = cell_coord(pts[3 * p], g.minx, g.inv_cell, g.res);
-    const int cy = cell_coord(pts[3 * p + 1], g.miny, g.inv_cell, g.res);
-    const int cz = cell_coord(pts[3 * p + 2], g.minz, g.inv_cell, g.res);
-    const int c = (cz * g.res + cy) * g.res + cx;
+    const int c = knn_cell_of(g, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]);
     cell_of[p] = c;
     atomicAdd(&counts[(size_t)n * stride + c], 1u);
 }
@@ -592,34 +620,143 @@ __global__ __launch_bounds__(1024) void knn_scan_single_kernel(const uint32_t *_
         p4 += c[i + 4096]; p5 += c[i + 5120]; p6 += c[i + 6144]; p7 += c[i + 7168];
     }
     for (; i < lim; i += 1024) p0 += c[i];
-    uint32_t part = ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    const uint32_t part = wave_xor_sum(((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)));
     const int c0 = lim + tid;
     const uint32_t v = c0 < cells ? c[c0] : 0u;
-    uint32_t incl = v;
+    if (lane == 0) wave_pre[wid] = part;   // (published by the barrier of the scan)
+    uint32_t total, prefix = 0;
+    const uint32_t own = block_excl_scan<16>(v, wave_tot, total);
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    if (lane == 0) wave_pre[wid] = part;
-    __syncthreads();
-    uint32_t before = 0, total = 0, prefix = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const uint32_t t = wave_tot[w];
-        before += (w < wid) ? t : 0u;
-        total += t;
-        prefix += wave_pre[w];
-    }
-    const uint32_t run = prefix + before + incl - v;
+    for (int w = 0; w < 16; ++w) prefix += wave_pre[w];
+    const uint32_t run = prefix + own;
     if (c0 < cells) {
         offsets[(size_t)n * stride + c0] = run;
         cursor[(size_t)n * stride + c0] = run;
     }
     if (tid == 0 && (b + 1) * KNN_SCAN_BLOCK >= cells) offsets[(size_t)n * stride + cells] = prefix + total;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the two query kernels share.  `best` is a query's ascending list of K squared distances, `bid` the ids that go
+// with them (FULL only), padded with (inf, 0x7fffffff); kk = min(K asked for, points in the cloud) entries count.
+// The lists stay in registers only while every entry that feeds a select is a VALUE, which the empty
+// `asm volatile("" : "+v"(x))` below makes it: left alone, the compiler rewrites select(c, a[i], a[j]) as a LOAD from
+// select(c, &a[i], &a[j]), which pins the array in scratch memory (or LDS) and puts loads and stores into the loops.
+// ---------------------------------------------------------------------------------------------------------------
+// (distance, id) total order; ids are unique within a cloud, the padding entries (inf, 0x7fffffff) compare equal
+// (bitwise | and &: the short-circuit forms compile to two nested exec-mask branches per comparison)
+__device__ __forceinline__ bool knn_less(float da, int ia, float db, int ib) { return (da < db) | ((da == db) & (ia < ib)); }
+
+// One candidate: keep the K best in (distance, id) order (FULL: deterministic lists whatever the cell order) or by
+// distance (K-th only; `id` is not read).
+template <int K, bool FULL>
+__device__ __forceinline__ void knn_insert(float (&best)[K], int (&bid)[FULL ? K : 1], float d2, int id)
+{
+    if (FULL) {
+        if (knn_less(d2, id, best[K - 1], bid[FULL ? K - 1 : 0])) {
+            bool lt[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) lt[k] = knn_less(d2, id, best[k], bid[FULL ? k : 0]);
+#pragma unroll
+            for (int k = K - 1; k >= 1; --k) {
+                float pb = best[k - 1];
+                int pi = bid[FULL ? k - 1 : 0];
+                asm volatile("" : "+v"(pb), "+v"(pi));   // (values, see above)
+                best[k] = lt[k - 1] ? pb : (lt[k] ? d2 : best[k]);
+                bid[FULL ? k : 0] = lt[k - 1] ? pi : (lt[k] ? id : bid[FULL ? k : 0]);
+            }
+            best[0] = lt[0] ? d2 : best[0];
+            bid[0] = lt[0] ? id : bid[0];
+        }
+    } else if (d2 < best[K - 1]) {
+#pragma unroll
+        for (int k = K - 1; k >= 1; --k) {
+            const bool sh = d2 < best[k - 1];
+            best[k] = sh ? best[k - 1] : (d2 < best[k] ? d2 : best[k]);
+        }
+        best[0] = d2 < best[0] ? d2 : best[0];
+    }
+}
+
+// Distance from the query (qx, qy, qz) in cell (cx, cy, cz) to the boundary of the block of cells within `ring` of its own: an exact
+// lower bound for every point not yet visited, less a slack for the fp32 cell-boundary arithmetic.  Faces that coincide
+// with the grid boundary have nothing behind them: +inf when no face is open.
+__device__ __forceinline__ float knn_ring_bound(const KnnGrid &g, int cx, int cy, int cz, int ring, float qx, float qy, float qz)
+{
+    float bound = __builtin_huge_valf();
+    if (cx - ring > 0) bound = fminf(bound, qx - (g.minx + (float)(cx - ring) * g.cell));
+    if (cx + ring < g.res - 1) bound = fminf(bound, (g.minx + (float)(cx + ring + 1) * g.cell) - qx);
+    if (cy - ring > 0) bound = fminf(bound, qy - (g.miny + (float)(cy - ring) * g.cell));
+    if (cy + ring < g.res - 1) bound = fminf(bound, (g.miny + (float)(cy + ring + 1) * g.cell) - qy);
+    if (cz - ring > 0) bound = fminf(bound, qz - (g.minz + (float)(cz - ring) * g.cell));
+    if (cz + ring < g.res - 1) bound = fminf(bound, (g.minz + (float)(cz + ring + 1) * g.cell) - qz);
+    return bound - 1e-6f * fmaxf(fabsf(bound), g.cell);
+}
+
+// Is the search finished after a ring?  Yes when every cell has been visited, or when the K-th distance found is
+// provably final (<= the distance to the unvisited region).  Fixed-radius statistic (r2 > 0, K-th only): nothing beyond
+// r counts, and everything not yet visited is farther than `bound`.  (knn_query_kernel's K-th distance instances carry these
+// two tests written out, for speed: a change here is a change there.)
+template <bool FULL>
+__device__ __forceinline__ bool knn_search_done(float bound, float kth, float r2)
+{
+    if (bound == __builtin_huge_valf() || (bound > 0.0f && kth <= bound * bound)) return true;
+    return !FULL && r2 > 0.0f && bound > 0.0f && bound * bound > r2;
+}
+
+// The K-th distance among the kk entries that count (fewer points than K: the farthest available).
+template <int K>
+__device__ __forceinline__ float knn_kth_of(const float (&best)[K], int kk)
+{
+    float kth = best[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        float b = best[k];
+        asm volatile("" : "+v"(b));   // (a value, see above)
+        kth = (k < kk) ? b : kth;
+    }
+    return kth;
+}
+
+// What a packed slot outside every cloud gets: a zero list, or a zero in the K-th distance row `kth_row`.
+template <bool FULL>
+__device__ __forceinline__ void knn_write_no_cloud(int64_t slot, int Krt, float *__restrict__ kth_row, float *__restrict__ dists,
+                                                   int64_t *__restrict__ idx)
+{
+    if (FULL) {
+        for (int k = 0; k < Krt; ++k) { dists[slot * Krt + k] = 0.0f; idx[slot * Krt + k] = 0; }
+    } else {
+        kth_row[slot] = 0.0f;
+    }
+}
+
+// What query point p (first packed slot of its cloud: f0) reports.  FULL: its list, zero-padded behind kk entries.
+// Otherwise the statistic, and (!VIEW, dk_out given) the K-th distance itself, inf when the cloud has fewer than K points.
+template <int K, bool FULL, bool VIEW>
+__device__ __forceinline__ void knn_write_result(const float (&best)[K], const int (&bid)[FULL ? K : 1], int kk, int Krt, int64_t p,
+                                                 int64_t f0, float r2, float *__restrict__ kth_sqdist, float *__restrict__ dists,
+                                                 int64_t *__restrict__ idx, float *__restrict__ dk_out)
+{
+    if (FULL) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (k < Krt) {
+                dists[p * Krt + k] = k < kk ? best[k] : 0.0f;
+                idx[p * Krt + k] = k < kk ? (int64_t)bid[FULL ? k : 0] - f0 : 0;
+            }
+        return;
+    }
+    float kth = knn_kth_of<K>(best, kk);
+    if (!VIEW && dk_out != nullptr) dk_out[p] = kk < Krt ? __builtin_huge_valf() : kth;
+    if (r2 > 0.0f) {
+        // fixed-radius semantics of the reference's default neighbour search (frnn_grid_points(K, r), rasterizer.py:317-326):
+        // neighbours beyond r come back as -1 and the statistic is the MAX over the K - 1 returned distances -- the farthest
+        // neighbour found within r, or -1 for a point without any
+        kth = -1.0f;
+#pragma unroll
+        for (int k = 1; k < K; ++k) kth = (k < kk && best[k] <= r2) ? best[k] : kth;
+    }
+    kth_sqdist[p] = kth;
 }
 
 // FULL = false: K-th squared distance only (kth_sqdist (P,)).  FULL = true: the whole neighbour list, ascending in
@@ -644,12 +781,8 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float *__restrict_
     if ((role == 1 && skip) || (role == 2 && !skip)) return;   // (the launch next to this one takes the cloud)
     const int n = find_cloud(slot, first_idx, num_pts, N);
     if (n < 0) {  // packed slot outside every cloud
-        if (FULL) {
-            for (int k = 0; k < Krt; ++k) { dists[slot * Krt + k] = 0.0f; idx[slot * Krt + k] = 0; }
-        } else {
-            // (one cloud, several cameras: the slot of THIS camera's row -- every row of the result is defined everywhere)
-            kth_sqdist[(VIEW && view.mode == 1 ? (size_t)blockIdx.y * (size_t)P : (size_t)0) + (size_t)slot] = 0.0f;
-        }
+        // (one cloud, several cameras: the slot of THIS camera's row -- every row of the result is defined everywhere)
+        knn_write_no_cloud<FULL>(slot, Krt, kth_sqdist + (VIEW && view.mode == 1 ? (size_t)blockIdx.y * (size_t)P : (size_t)0), dists, idx);
         return;
     }
     const KnnGrid g = grids[n];
@@ -661,19 +794,17 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float *__restrict_
     const float4 self = sorted[slot];
     const int64_t p = (int64_t)__float_as_int(self.w);
     const float qx = self.x, qy = self.y, qz = self.z;
-    float v2 = 0.f, v6 = 0.f, v10 = 0.f, v14 = 0.f, zn = 0.f, zf = 0.f;
+    KnnCamera camera = {};
     if (VIEW) {
         const int cam = view.mode == 1 ? (int)blockIdx.y : n;
         if (view.mode == 1 && view.culls[cam] == 0u) return;   // (the row is a copy: knn_view_rows_kernel)
-        const float *vm = view.V + 16 * cam;
-        v2 = vm[2]; v6 = vm[6]; v10 = vm[10]; v14 = vm[14]; zn = view.znear[cam]; zf = view.zfar[cam];
+        camera = KnnCamera::load(view.V, view.znear, view.zfar, cam);
         if (view.mode == 1) kth_sqdist += (size_t)cam * (size_t)P;
-        if (!knn_kept(qx, qy, qz, v2, v6, v10, v14, zn, zf)) { kth_sqdist[p] = 0.0f; return; }
-        if (knn_view_shortcut(view.culls[cam], qx, qy, qz, v2, v6, v10, v14, zn, zf, plain_dk[p], r2)) { kth_sqdist[p] = plain_stat[p]; return; }
+        if (!camera.kept(qx, qy, qz)) { kth_sqdist[p] = 0.0f; return; }
+        if (knn_view_shortcut(view.culls[cam], qx, qy, qz, camera, plain_dk[p], r2)) { kth_sqdist[p] = plain_stat[p]; return; }
     }
-    const int cx = cell_coord(qx, g.minx, g.inv_cell, g.res);
-    const int cy = cell_coord(qy, g.miny, g.inv_cell, g.res);
-    const int cz = cell_coord(qz, g.minz, g.inv_cell, g.res);
+    const int3 cell = knn_cell_coords(g, qx, qy, qz);
+    const int cx = cell.x, cy = cell.y, cz = cell.z;
     float best[K];
     int bid[FULL ? K : 1];
 #pragma unroll
@@ -685,41 +816,11 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float *__restrict_
         if (!FULL) kth_sqdist[p] = 0.0f;
         return;
     }
-    // One candidate: keep the K best in (distance, id) order (FULL) or by distance (kth only).
     auto consider = [&](const float4 q) __attribute__((always_inline)) {
         const float dx = q.x - qx, dy = q.y - qy, dz = q.z - qz;
         float d2 = dx * dx + dy * dy + dz * dz;
-        if (VIEW && !knn_kept(q.x, q.y, q.z, v2, v6, v10, v14, zn, zf)) d2 = __builtin_huge_valf();   // the camera drops it
-        if (FULL) {
-            // total order (distance, id): deterministic lists whatever the cell order
-            const int id = __float_as_int(q.w);
-            // bitwise | and &: the short-circuit forms compile to two nested exec-mask branches per comparison
-            if ((d2 < best[K - 1]) | ((d2 == best[K - 1]) & (id < bid[FULL ? K - 1 : 0]))) {
-                bool lt[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) lt[k] = (d2 < best[k]) | ((d2 == best[k]) & (id < bid[FULL ? k : 0]));
-#pragma unroll
-                for (int k = K - 1; k >= 1; --k) {
-                    // the empty asm keeps the operands values: left alone, the compiler rewrites select(c, bid[k-1],
-                    // bid[k]) as a LOAD from select(c, &bid[k-1], &bid[k]), which pins bid[] in scratch memory and
-                    // puts scratch loads/stores into this loop
-                    float pb = best[k - 1];
-                    int pi = bid[k - 1];
-                    asm volatile("" : "+v"(pb), "+v"(pi));
-                    best[k] = lt[k - 1] ? pb : (lt[k] ? d2 : best[k]);
-                    bid[k] = lt[k - 1] ? pi : (lt[k] ? id : bid[k]);
-                }
-                best[0] = lt[0] ? d2 : best[0];
-                bid[0] = lt[0] ? id : bid[0];
-            }
-        } else if (d2 < best[K - 1]) {
-#pragma unroll
-            for (int k = K - 1; k >= 1; --k) {
-                const bool sh = d2 < best[k - 1];
-                best[k] = sh ? best[k - 1] : (d2 < best[k] ? d2 : best[k]);
-            }
-            best[0] = d2 < best[0] ? d2 : best[0];
-        }
+        if (VIEW && !camera.kept(q.x, q.y, q.z)) d2 = __builtin_huge_valf();   // the camera drops it
+        knn_insert<K, FULL>(best, bid, d2, __float_as_int(q.w));
     };
     // Candidates [s, e) of the cell-sorted array: cells that are consecutive along x are consecutive in memory, so a
     // whole (z, y) row of the search block is ONE contiguous range.  Four candidates are requested per memory round
@@ -763,7 +864,7 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float *__restrict_
     };
     if (skip) {
         // own cell dense (its points lie along a Morton curve): the neighbours of the query's slot are neighbours in space
-        const int c_own = (cz * g.res + cy) * g.res + cx;
+        const int c_own = knn_cell_index(g, cx, cy, cz);
         const uint32_t cs = off[c_own], ce = off[c_own + 1];
         if (ce - cs > (uint32_t)KNN_DENSE) {
             const uint32_t me = (uint32_t)(slot - f0);
@@ -813,46 +914,18 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float *__restrict_
             }
             visit(s, e);
         }
-        // distance from the query to the boundary of the visited block (exact lower bound for unvisited points);
-        // faces that coincide with the grid boundary have nothing behind them
-        float bound = __builtin_huge_valf();
-        if (cx - ring > 0) bound = fminf(bound, qx - (g.minx + (float)(cx - ring) * g.cell));
-        if (cx + ring < g.res - 1) bound = fminf(bound, (g.minx + (float)(cx + ring + 1) * g.cell) - qx);
-        if (cy - ring > 0) bound = fminf(bound, qy - (g.miny + (float)(cy - ring) * g.cell));
-        if (cy + ring < g.res - 1) bound = fminf(bound, (g.miny + (float)(cy + ring + 1) * g.cell) - qy);
-        if (cz - ring > 0) bound = fminf(bound, qz - (g.minz + (float)(cz - ring) * g.cell));
-        if (cz + ring < g.res - 1) bound = fminf(bound, (g.minz + (float)(cz + ring + 1) * g.cell) - qz);
-        // slack for the fp32 cell-boundary arithmetic
-        bound = bound - 1e-6f * fmaxf(fabsf(bound), g.cell);
-        float kth = best[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) kth = (k < kk) ? best[k] : kth;
-        if (bound == __builtin_huge_valf() || (bound > 0.0f && kth <= bound * bound)) break;
-        // fixed-radius statistic: nothing beyond r counts, and everything not yet visited is farther than `bound`
-        if (!FULL && r2 > 0.0f && bound > 0.0f && bound * bound > r2) break;
+        const float bound = knn_ring_bound(g, cx, cy, cz, ring, qx, qy, qz), kth = knn_kth_of<K>(best, kk);
+        if constexpr (FULL) {
+            if (knn_search_done<true>(bound, kth, r2)) break;
+        } else {
+            // knn_search_done, the statement of record, written out: called here it costs the K-th distance instances
+            // 1.3 % of a whole call at 131k points; written out for the lists it costs those 0.5 to 1 %
+            // (profiles/knn_device_refactor.txt)
+            if (bound == __builtin_huge_valf() || (bound > 0.0f && kth <= bound * bound)) break;
+            if (r2 > 0.0f && bound > 0.0f && bound * bound > r2) break;
+        }
     }
-    if (FULL) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (k < Krt) {
-                dists[p * Krt + k] = k < kk ? best[k] : 0.0f;
-                idx[p * Krt + k] = k < kk ? (int64_t)bid[k] - f0 : 0;
-            }
-        return;
-    }
-    float kth = best[0];
-#pragma unroll
-    for (int k = 1; k < K; ++k) kth = (k < kk) ? best[k] : kth;
-    if (!VIEW && dk_out != nullptr) dk_out[p] = kk < Krt ? __builtin_huge_valf() : kth;
-    if (r2 > 0.0f) {
-        // fixed-radius semantics of the reference's default neighbour search (frnn_grid_points(K, r), rasterizer.py:317-326):
-        // neighbours beyond r come back as -1 and the statistic is the MAX over the K - 1 returned distances -- the farthest
-        // neighbour found within r, or -1 for a point without any
-        kth = -1.0f;
-#pragma unroll
-        for (int k = 1; k < K; ++k) kth = (k < kk && best[k] <= r2) ? best[k] : kth;
-    }
-    kth_sqdist[p] = kth;
+    knn_write_result<K, FULL, VIEW>(best, bid, kk, Krt, p, f0, r2, kth_sqdist, dists, idx, dk_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -873,9 +946,6 @@ __device__ __forceinline__ float knn_dpp_f(float v)
 }
 template <int CTRL>
 __device__ __forceinline__ int knn_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-
-// (distance, id) total order; ids are unique within a cloud, the padding entries (inf, 0x7fffffff) compare equal
-__device__ __forceinline__ bool knn_less(float da, int ia, float db, int ib) { return (da < db) | ((da == db) & (ia < ib)); }
 
 // this lane's ascending K-list merged with the list of the lane CTRL maps to: min(A[i], B[K-1-i]) picks the K smallest of
 // the union as a bitonic sequence, an odd-even transposition network sorts it (see merge_round in raster_forward.hip)
@@ -946,14 +1016,8 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
     if (slot >= P) continue;   // (whole DPP rows leave together)
     const int n = find_cloud(slot, first_idx, num_pts, N);
     if (n < 0) {  // packed slot outside every cloud
-        if (sub == 0) {
-            if (FULL) {
-                for (int k = 0; k < Krt; ++k) { dists[slot * Krt + k] = 0.0f; idx[slot * Krt + k] = 0; }
-            } else {
-                // (one cloud, several cameras: the slot of THIS camera's row -- every row of the result is defined everywhere)
-                kth_base[(walk ? (size_t)cam_y * (size_t)P : (size_t)0) + (size_t)slot] = 0.0f;
-            }
-        }
+        // (one cloud, several cameras: the slot of THIS camera's row -- every row of the result is defined everywhere)
+        if (sub == 0) knn_write_no_cloud<FULL>(slot, Krt, kth_base + (walk ? (size_t)cam_y * (size_t)P : (size_t)0), dists, idx);
         continue;
     }
     const KnnGrid g = grids[n];
@@ -963,24 +1027,22 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
     const float4 self = sorted[slot];   // the slot-th point of the cell-sorted order
     const int64_t p = (int64_t)__float_as_int(self.w);
     const float qx = self.x, qy = self.y, qz = self.z;
-    float v2 = 0.f, v6 = 0.f, v10 = 0.f, v14 = 0.f, zn = 0.f, zf = 0.f;
+    KnnCamera camera = {};
     if (VIEW) {
         const int cam = view.mode == 1 ? cam_y : n;
-        const float *vm = view.V + 16 * cam;
-        v2 = vm[2]; v6 = vm[6]; v10 = vm[10]; v14 = vm[14]; zn = view.znear[cam]; zf = view.zfar[cam];
+        camera = KnnCamera::load(view.V, view.znear, view.zfar, cam);
         if (view.mode == 1) kth_sqdist = kth_base + (size_t)cam * (size_t)P;
-        if (!knn_kept(qx, qy, qz, v2, v6, v10, v14, zn, zf)) {   // (the whole 16-lane group shares the query: leaves together)
+        if (!camera.kept(qx, qy, qz)) {   // (the whole 16-lane group shares the query: leaves together)
             if (sub == 0) kth_sqdist[p] = 0.0f;
             continue;
         }
-        if (knn_view_shortcut(view.culls[cam], qx, qy, qz, v2, v6, v10, v14, zn, zf, plain_dk[p], r2)) {
+        if (knn_view_shortcut(view.culls[cam], qx, qy, qz, camera, plain_dk[p], r2)) {
             if (sub == 0) kth_sqdist[p] = plain_stat[p];
             continue;
         }
     }
-    const int cx = cell_coord(qx, g.minx, g.inv_cell, g.res);
-    const int cy = cell_coord(qy, g.miny, g.inv_cell, g.res);
-    const int cz = cell_coord(qz, g.minz, g.inv_cell, g.res);
+    const int3 cell = knn_cell_coords(g, qx, qy, qz);
+    const int cx = cell.x, cy = cell.y, cz = cell.z;
     float best[K];
     int bid[FULL ? K : 1];
 #pragma unroll
@@ -994,33 +1056,11 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
     }
     auto consider = [&](const float4 q, bool on) __attribute__((always_inline)) {
         const float dx = q.x - qx, dy = q.y - qy, dz = q.z - qz;
-        if (VIEW) on = on && knn_kept(q.x, q.y, q.z, v2, v6, v10, v14, zn, zf);   // the camera drops it
+        if (VIEW) on = on && camera.kept(q.x, q.y, q.z);   // the camera drops it
+        // a lane without a candidate (`on` down) offers the padding entry, which enters no list
         const float d2 = on ? dx * dx + dy * dy + dz * dz : __builtin_huge_valf();
-        if (FULL) {
-            const int id = on ? __float_as_int(q.w) : 0x7fffffff;
-            if (knn_less(d2, id, best[K - 1], bid[FULL ? K - 1 : 0])) {
-                bool lt[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) lt[k] = knn_less(d2, id, best[k], bid[FULL ? k : 0]);
-#pragma unroll
-                for (int k = K - 1; k >= 1; --k) {
-                    float pb = best[k - 1];
-                    int pi = bid[FULL ? k - 1 : 0];
-                    asm volatile("" : "+v"(pb), "+v"(pi));   // (keeps bid[] out of scratch, see knn_query_kernel)
-                    best[k] = lt[k - 1] ? pb : (lt[k] ? d2 : best[k]);
-                    bid[FULL ? k : 0] = lt[k - 1] ? pi : (lt[k] ? id : bid[FULL ? k : 0]);
-                }
-                best[0] = lt[0] ? d2 : best[0];
-                bid[0] = lt[0] ? id : bid[0];
-            }
-        } else if (d2 < best[K - 1]) {
-#pragma unroll
-            for (int k = K - 1; k >= 1; --k) {
-                const bool sh = d2 < best[k - 1];
-                best[k] = sh ? best[k - 1] : (d2 < best[k] ? d2 : best[k]);
-            }
-            best[0] = d2 < best[0] ? d2 : best[0];
-        }
+        const int id = on ? __float_as_int(q.w) : 0x7fffffff;
+        knn_insert<K, FULL>(best, bid, d2, id);
     };
     // candidates [s, e) of the cell-sorted array, every KNN_LPQ-th one for this lane: the group's 16 loads of a trip are
     // one contiguous 256-byte run; two trips are requested together
@@ -1032,10 +1072,10 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
     uint32_t seed_lo = 0, seed_hi = 0;
     const int gsh = (int)(threadIdx.x & 48u);   // bit position of the group's lanes in the wavefront's ballot
     auto merge_all = [&]() __attribute__((always_inline)) {
-        knn_merge_round<K, FULL, 0xB1>(best, bid);
-        knn_merge_round<K, FULL, 0x4E>(best, bid);
-        knn_merge_round<K, FULL, 0x141>(best, bid);
-        knn_merge_round<K, FULL, 0x140>(best, bid);
+        knn_merge_round<K, FULL, 0xB1>(best, bid);    // quad_perm [1,0,3,2]
+        knn_merge_round<K, FULL, 0x4E>(best, bid);    // quad_perm [2,3,0,1]
+        knn_merge_round<K, FULL, 0x141>(best, bid);   // row_half_mirror
+        knn_merge_round<K, FULL, 0x140>(best, bid);   // row_mirror
     };
     auto keep_lane0 = [&]() __attribute__((always_inline)) {   // lane 0 carries the merged list, the others start empty (nothing is counted twice)
         const bool drop = sub != 0;   // (selects on values: a branch around stores to bid[] sends the array to scratch memory)
@@ -1100,7 +1140,7 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
     };
     if (skip) {
         // own cell dense (its points lie along a Morton curve): the neighbours of the query's slot are neighbours in space
-        const int c_own = (cz * g.res + cy) * g.res + cx;
+        const int c_own = knn_cell_index(g, cx, cy, cz);
         const uint32_t cs = off[c_own], ce = off[c_own + 1];
         if (ce - cs > (uint32_t)KNN_DENSE) {
             const uint32_t me = (uint32_t)(slot - f0);
@@ -1193,25 +1233,9 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
         }
         }   // (SKIP)
         // the group's K best: four merge rounds inside the DPP row, every lane ends with the same list
-        knn_merge_round<K, FULL, 0xB1>(best, bid);    // quad_perm [1,0,3,2]
-        knn_merge_round<K, FULL, 0x4E>(best, bid);    // quad_perm [2,3,0,1]
-        knn_merge_round<K, FULL, 0x141>(best, bid);   // row_half_mirror
-        knn_merge_round<K, FULL, 0x140>(best, bid);   // row_mirror
+        merge_all();
         kb = best[K - 1];
-        float bound = __builtin_huge_valf();
-        if (cx - ring > 0) bound = fminf(bound, qx - (g.minx + (float)(cx - ring) * g.cell));
-        if (cx + ring < g.res - 1) bound = fminf(bound, (g.minx + (float)(cx + ring + 1) * g.cell) - qx);
-        if (cy - ring > 0) bound = fminf(bound, qy - (g.miny + (float)(cy - ring) * g.cell));
-        if (cy + ring < g.res - 1) bound = fminf(bound, (g.miny + (float)(cy + ring + 1) * g.cell) - qy);
-        if (cz - ring > 0) bound = fminf(bound, qz - (g.minz + (float)(cz - ring) * g.cell));
-        if (cz + ring < g.res - 1) bound = fminf(bound, (g.minz + (float)(cz + ring + 1) * g.cell) - qz);
-        bound = bound - 1e-6f * fmaxf(fabsf(bound), g.cell);
-        float kth = best[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) kth = (k < kk) ? best[k] : kth;
-        if (bound == __builtin_huge_valf() || (bound > 0.0f && kth <= bound * bound)) break;
-        // fixed-radius statistic: nothing beyond r counts, and everything not yet visited is farther than `bound`
-        if (!FULL && r2 > 0.0f && bound > 0.0f && bound * bound > r2) break;
+        if (knn_search_done<FULL>(knn_ring_bound(g, cx, cy, cz, ring, qx, qy, qz), knn_kth_of<K>(best, kk), r2)) break;
         if (sub != 0) {   // next ring: lane 0 carries the merged list, the others start empty (nothing is counted twice)
 #pragma unroll
             for (int k = 0; k < K; ++k) best[k] = __builtin_huge_valf();
@@ -1219,34 +1243,7 @@ __global__ __launch_bounds__(256) void knn_query_coop_kernel(const float *__rest
             for (int k = 0; k < (FULL ? K : 1); ++k) bid[k] = 0x7fffffff;
         }
     }
-    if (sub != 0) continue;
-    if (!FULL && !VIEW && dk_out != nullptr) {
-        float dk = best[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) dk = (k < kk) ? best[k] : dk;
-        dk_out[p] = kk < Krt ? __builtin_huge_valf() : dk;
-    }
-    if (FULL) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (k < Krt) {
-                dists[p * Krt + k] = k < kk ? best[k] : 0.0f;
-                idx[p * Krt + k] = k < kk ? (int64_t)bid[FULL ? k : 0] - f0 : 0;
-            }
-        continue;
-    }
-    float kth = best[0];
-#pragma unroll
-    for (int k = 1; k < K; ++k) kth = (k < kk) ? best[k] : kth;
-    if (r2 > 0.0f) {
-        // fixed-radius semantics of the reference's default neighbour search (frnn_grid_points(K, r), rasterizer.py:317-326):
-        // neighbours beyond r come back as -1 and the statistic is the MAX over the K - 1 returned distances -- the farthest
-        // neighbour found within r, or -1 for a point without any
-        kth = -1.0f;
-#pragma unroll
-        for (int k = 1; k < K; ++k) kth = (k < kk && best[k] <= r2) ? best[k] : kth;
-    }
-    kth_sqdist[p] = kth;
+    if (sub == 0) knn_write_result<K, FULL, VIEW>(best, bid, kk, Krt, p, f0, r2, kth_sqdist, dists, idx, dk_out);
     }   // (chunks)
     }   // (cameras)
 }
@@ -1269,6 +1266,7 @@ __global__ __launch_bounds__(1024) void cloud_mean_kernel(const float *__restric
     }
     for (; i < cnt; i += 1024) a0 += (double)(vals[f0 + i] * scale);
     double acc = (a0 + a1) + (a2 + a3);
+    // wave_xor_sum, the statement of record, written out: called here the load loop above is scheduled differently, 0.5 us
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if ((tid & 63) == 0) part[tid >> 6] = acc;
@@ -1299,8 +1297,7 @@ __global__ __launch_bounds__(1024) void renderable_sum_kernel(const float *__res
     __shared__ double psum[16], pcnt[16];
     const int n = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
     const int64_t f0 = shared ? 0 : first_idx[n], cnt = num_pts[n];
-    const float *v = V + 16 * n;
-    const float v2 = v[2], v6 = v[6], v10 = v[10], v14 = v[14], zn = znear[n], zf = zfar[n];
+    const KnnCamera camera = KnnCamera::load(V, znear, zfar, n);
     double a = 0.0;
     float c = 0.f;
     // block b of a camera takes the points b * 1024 + tid + k * (RENDERABLE_BLOCKS * 1024): a fixed assignment, so the sums
@@ -1319,15 +1316,13 @@ __global__ __launch_bounds__(1024) void renderable_sum_kernel(const float *__res
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const float zview = x[u] * v2 + y[u] * v6 + z[u] * v10 + 1.0f * v14;   // the expression of setup_point_compute
-            const bool ok = in[u] && (zview >= zn) && (zview <= zf);
+            const bool ok = in[u] && camera.kept(x[u], y[u], z[u]);
             a += ok ? (double)(q[u] * scale) : 0.0;
             c += ok ? 1.f : 0.f;
         }
     }
-    double cc = (double)c;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); cc += __shfl_xor(cc, o); }
+    a = wave_xor_sum(a);
+    const double cc = wave_xor_sum((double)c);
     if ((tid & 63) == 0) { psum[tid >> 6] = a; pcnt[tid >> 6] = cc; }
     __syncthreads();
     if (tid == 0) {

@@ -88,7 +88,7 @@ def brute_radius_stat(points, K, r):
 
 
 def view_depth32(cloud, V_n):
-    """view depth with the kernel's expression, every operation rounded to fp32 (knn_kept in knn.hip)"""
+    """view depth with the kernel's expression, every operation rounded to fp32 (KnnCamera::kept in knn.hip)"""
     c, V = cloud.astype(np.float32), V_n.astype(np.float32)
     return ((c[:, 0] * V[0, 2] + c[:, 1] * V[1, 2]) + c[:, 2] * V[2, 2]) + np.float32(1.0) * V[3, 2]
 
