@@ -37,12 +37,12 @@ def calling_thread_backward():
 
 
 _CLOUD_OPS = ("upsample", "upsample_clouds", "remove_outliers", "denoise_normals", "project_to_latent_surface",
-              "sample_farthest_points", "subsample")
+              "sample_farthest_points", "subsample", "estimate_normals", "orient_normals")
 
 
 def __getattr__(name):
     """``dss_amd.upsample`` / ``upsample_clouds`` / ``remove_outliers`` / ``denoise_normals`` / ``project_to_latent_surface``
-    / ``sample_farthest_points`` / ``subsample`` (dss_amd/cloud_ops.py), imported on first use so that
+    / ``sample_farthest_points`` / ``subsample`` / ``estimate_normals`` / ``orient_normals`` (dss_amd/cloud_ops.py), imported on first use so that
     ``import dss_amd`` itself stays free of torch."""
     if name in _CLOUD_OPS:
         from . import cloud_ops

@@ -104,6 +104,9 @@ SIGNATURES = {
     "dss_rimls_step": (_c_int, [_c_vp] * 8 + [_c_int, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     "dss_farthest_points_workspace": (_c_sz, [_c_int, _c_i64]),
     "dss_farthest_points": (_c_int, [_c_vp] * 5 + [_c_int, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "dss_disambiguate_normals": (_c_int, [_c_vp] * 5 + [_c_int, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    "dss_orient_normals_workspace": (_c_sz, [_c_int, _c_i64]),
+    "dss_orient_normals": (_c_int, [_c_vp] * 5 + [_c_int, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "dss_blend_forward": (_c_int, [_c_vp] * 5 + [_c_int] * 5 + [_c_vp, _c_vp, _c_vp]),
     "dss_local_frames": (_c_int, [_c_vp] * 4 + [_c_int, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     "dss_point_setup": (_c_int, [_c_vp] * 12 + [_c_int, _c_i64, _c_int, _c_int, _c_int, _c_f32, _c_f32]

@@ -146,6 +146,24 @@ class PointClouds3D:
     def features_padded(self):
         return self._padded(self._features)
 
+    def estimate_normals(self, neighborhood_size: int = 16, disambiguate_directions: bool = True,
+                         assign_to_self: bool = False, orientation: Optional[str] = None):
+        """Normals of every cloud from the PCA of its ``neighborhood_size`` nearest points -> padded (N,P_max,3), the
+        method of DSS/core/cloud.py:210-258.  ``disambiguate_directions=True`` is the reference's per-neighbourhood sign
+        (``orientation="local"`` of `dss_amd.cloud_ops.estimate_normals`), ``False`` leaves the sign of the eigen-solver
+        (``"none"``); ``orientation``, when given, overrides both: ``"consistent"`` is the one that makes the cloud
+        renderable (``"viewpoint"`` needs the free function).  ``assign_to_self`` stores the result as the cloud's normals,
+        replacing any it had."""
+        from . import cloud_ops
+        if orientation is None:
+            orientation = "local" if disambiguate_directions else "none"
+        normals = cloud_ops.estimate_normals(self, neighborhood_size=neighborhood_size, orientation=orientation,
+                                             orientation_neighbours=min(8, int(neighborhood_size)))
+        if assign_to_self:
+            self._normals = [normals[n, :p.shape[0]] for n, p in enumerate(self._points)]
+            self._packed_cache.pop("normals", None)
+        return normals
+
     def extend(self, N: int) -> "PointClouds3D":
         """N copies of every cloud (shared autograd graph), like Pointclouds.extend."""
         rep = lambda lst: None if lst is None else [t for t in lst for _ in range(N)]

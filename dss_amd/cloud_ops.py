@@ -9,7 +9,10 @@ is DESIGN 4.15.  Nothing here is differentiable: the reference uses these tools 
 phases.  The one that THINS a cloud evenly: `sample_farthest_points` (pytorch3d's call) and `subsample` pick a subset by
 farthest point sampling -- every new point the one farthest from those already picked, ties to the smallest id, no point
 picked twice -- in one persistent workgroup per cloud (``dss_amd/csrc/sampling.hip``); `subsample` with
-``method="random"`` is the reference's `subsample_randomly` (:260-279), which keeps the density of its input.
+``method="random"`` is the reference's `subsample_randomly` (:260-279), which keeps the density of its input.  The one that
+gives a cloud its NORMALS: `estimate_normals` (:210-258) takes the PCA direction of every neighbourhood and chooses its sign,
+by default so that every connected part shows one side; `orient_normals` does the same for normals that exist
+(``dss_amd/csrc/normals.hip``).
 """
 from typing import List, Optional, Sequence, Union
 
@@ -455,3 +458,126 @@ def subsample(point_clouds, n_points: Union[None, int, Sequence[int], torch.Tens
         keep = [torch.randperm(s, device=dev, generator=generator)[:k] for s, k in zip(sizes, counts)]
     pick = lambda lst: None if lst is None else [t.detach().index_select(0, k) for t, k in zip(lst, keep)]
     return PointClouds3D(pick(pts), pick(point_clouds.normals_list()), pick(point_clouds.features_list()))
+
+
+ORIENTATIONS = ("none", "local", "viewpoint", "consistent")
+
+
+def _normals_points(who: str, points, num_points):
+    """Shapes and sizes that the two normal calls share -> (points (N,P,3), sizes).  Nothing is launched here."""
+    if isinstance(points, PointClouds3D):
+        if num_points is None:
+            num_points = [int(p.shape[0]) for p in points.points_list()]
+        points = points.points_padded()
+    if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3:
+        raise ValueError("%s expects padded points (N,P,3) or a PointClouds3D" % who)
+    N, P = points.shape[0], points.shape[1]
+    sizes = _host_ints(P if num_points is None else num_points, N, "num_points")
+    if any(s < 0 or s > P for s in sizes):
+        raise ValueError("num_points must lie in 0 .. P = %d" % P)
+    return points.detach(), sizes
+
+
+def _check_neighbourhood(who: str, sizes: Sequence[int], K: int) -> None:
+    if K < 1 or K > MAX_KNN:
+        raise ValueError("%s: neighborhood_size must be in 1 .. %d, got %d" % (who, MAX_KNN, K))
+    for n, s in enumerate(sizes):
+        if s <= K:
+            raise ValueError("%s: cloud %d has %d points, the neighbourhood size is %d" % (who, n, s, K))
+
+
+@torch.no_grad()
+def estimate_normals(points, num_points=None, neighborhood_size: int = 16, orientation: str = "consistent",
+                     orientation_neighbours: int = 8, viewpoint=None, return_curvature: bool = False):
+    """Unit normals of a cloud that has none -> normals (N,P,3), a new tensor, padding rows zero; with
+    ``return_curvature`` also the ascending eigenvalues (N,P,3) of every neighbourhood's covariance.
+
+    points (N,P,3) padded with ``num_points`` the N lengths (None: all P), or a ``PointClouds3D``.  The direction is the
+    axis of least variance of the ``neighborhood_size`` nearest points, the point itself included (``ops.knn_points``,
+    ``ops.local_frames``: `estimate_pointcloud_normals` of DSS/utils/mathHelper.py:113-147).  Its sign, by ``orientation``:
+
+    ``"none"``        as the eigen-solver leaves it.
+    ``"local"``       the reference's rule (Tombari's majority vote): towards the side on which most of the neighbourhood
+                      lies.  Decided per point; on a convex shape nearly every normal ends up pointing inward.
+    ``"viewpoint"``   towards ``viewpoint``, (3,) for all clouds or (N,3): for a scan taken from a known position.
+    ``"consistent"``  one side of the surface for every connected part: from the highest point, turned
+                      upwards, the sign spreads over the ``orientation_neighbours`` nearest points (the point itself
+                      counted) to the most parallel neighbours first, a fold being crossed only when nothing else is left.
+                      The sign of a whole part rests on its seed -- outward for a closed surface, whose highest point
+                      looks up -- and two sheets closer than the neighbourhood radius can be joined.
+
+    Every cloud is processed as if it were alone.  Not differentiable.  With sizes given as Python integers the call reads
+    nothing back from the device and can be captured in a graph.  Raises ValueError, before anything is launched, for wrong
+    shapes, ``neighborhood_size`` outside 1 .. 40, a cloud with no more than ``neighborhood_size`` points,
+    ``orientation_neighbours`` outside 2 .. ``neighborhood_size``, an unknown ``orientation`` and a ``viewpoint`` that is
+    missing or superfluous.  GPU tensors only: there is no CPU fallback."""
+    who = "estimate_normals"
+    K, KP = int(neighborhood_size), int(orientation_neighbours)
+    if orientation not in ORIENTATIONS:
+        raise ValueError("%s: orientation must be one of %s, got %r" % (who, ", ".join(map(repr, ORIENTATIONS)), orientation))
+    if (viewpoint is not None) != (orientation == "viewpoint"):
+        raise ValueError("%s: orientation='viewpoint' needs a viewpoint and no other orientation takes one" % who)
+    points, sizes = _normals_points(who, points, num_points)
+    N = len(sizes)
+    _check_neighbourhood(who, sizes, K)
+    if KP < 2 or KP > K:
+        raise ValueError("%s: orientation_neighbours must be in 2 .. neighborhood_size = %d, got %d" % (who, K, KP))
+    if viewpoint is not None:
+        viewpoint = torch.as_tensor(viewpoint, dtype=torch.float32)
+        if tuple(viewpoint.shape) not in ((3,), (N, 3)):
+            raise ValueError("%s: viewpoint must be (3,) or (N,3) = (%d,3), got %s" % (who, N, tuple(viewpoint.shape)))
+    _require_gpu_cloud(points)
+    dev = points.device
+    pts = _pack(points.to(torch.float32), sizes).contiguous()
+    first, num = _ranges(sizes, dev)
+    _, knn_idx = ops.knn_points(pts, first, num, K)
+    _, nrm, curvature = ops.local_frames(pts, knn_idx, first, num, return_curvature=True)
+    if orientation == "local":
+        nrm = ops.disambiguate_normals(pts, nrm, knn_idx, first, num)
+    elif orientation == "viewpoint":
+        nrm = ops.disambiguate_normals(pts, nrm, None, first, num, viewpoint.to(dev).expand(N, 3).contiguous())
+    elif orientation == "consistent":
+        nrm = ops.orient_normals(nrm, pts, knn_idx, first, num, KP)
+    out = _pad_to(nrm, sizes, points.shape[1])
+    return (out, _pad_to(curvature, sizes, points.shape[1])) if return_curvature else out
+
+
+@torch.no_grad()
+def orient_normals(points, normals, num_points=None, neighborhood_size: int = 8, return_parents: bool = False):
+    """One side of the surface for a cloud that already has normals, unsigned or inconsistently signed -> normals
+    (N,P,3), a new tensor: every input normal or its negative, padding rows zero; with ``return_parents`` also (N,P)
+    int64, the cloud-local id of the neighbour whose sign a point took, -1 for a seed and in the padding.
+
+    points, normals (N,P,3) padded with ``num_points`` the N lengths (None: all P), or a ``PointClouds3D`` (then
+    ``normals=None`` takes the cloud's own).  The propagation of `estimate_normals` with ``orientation="consistent"`` over
+    the ``neighborhood_size`` nearest points, the point itself counted.  Not differentiable; no
+    device-to-host read with host integers.  Raises ValueError, before anything is launched, for wrong shapes,
+    ``neighborhood_size`` outside 2 .. 40 and a cloud with no more than ``neighborhood_size`` points.  GPU tensors only:
+    there is no CPU fallback."""
+    who = "orient_normals"
+    K = int(neighborhood_size)
+    if isinstance(points, PointClouds3D) and normals is None:
+        normals = points.normals_padded()
+    points, sizes = _normals_points(who, points, num_points)
+    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape):
+        raise ValueError("%s expects normals of the points' shape %s" % (who, tuple(points.shape)))
+    if K < 2 or K > MAX_KNN:
+        raise ValueError("%s: neighborhood_size must be in 2 .. %d, got %d" % (who, MAX_KNN, K))
+    _check_neighbourhood(who, sizes, K)
+    _require_gpu_cloud(points)
+    if not normals.is_cuda:
+        raise RuntimeError("dss_amd: normals is on %s; the HIP path needs GPU tensors (no CPU fallback)" % normals.device)
+    dev = points.device
+    pts = _pack(points.to(torch.float32), sizes).contiguous()
+    nrm = _pack(normals.detach().to(torch.float32), sizes).contiguous()
+    first, num = _ranges(sizes, dev)
+    _, knn_idx = ops.knn_points(pts, first, num, K)
+    res = ops.orient_normals(nrm, pts, knn_idx, first, num, K, return_parents=return_parents)
+    if not return_parents:
+        return _pad_to(res, sizes, points.shape[1])
+    parents = torch.full((len(sizes), points.shape[1]), -1, dtype=_i64, device=dev)
+    f = 0
+    for n, s in enumerate(sizes):
+        parents[n, :s] = res[1][f:f + s]
+        f += s
+    return _pad_to(res[0], sizes, points.shape[1]), parents

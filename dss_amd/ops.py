@@ -1376,3 +1376,6 @@ from .smoothing_ops import denoise_normals, rimls_step  # noqa: E402,F401
 # and the kernel that thins a cloud evenly (sampling_ops.py; the public calls are dss_amd.cloud_ops.sample_farthest_points
 # and subsample)
 from .sampling_ops import farthest_points  # noqa: E402,F401
+# and the two kernels that give estimated normals a sign (normals_ops.py; the public calls are
+# dss_amd.cloud_ops.estimate_normals and orient_normals)
+from .normals_ops import disambiguate_normals, orient_normals  # noqa: E402,F401

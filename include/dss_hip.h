@@ -705,6 +705,62 @@ DSS_API int dss_farthest_points(const float *points /* (P,3) */, const int64_t *
                                 void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The sign of estimated normals.  dss_local_frames gives the PCA direction of every neighbourhood with an arbitrary sign;
+ * the reference's `PointClouds3D.estimate_normals` (DSS/core/cloud.py:210-258, utils/mathHelper.py:113-147) fixes it per
+ * neighbourhood, which leaves a cloud that cannot be rendered: one side of the surface is needed.
+ * Both entries: points, normals (P,3) packed; knn_idx (P,K) = the cloud-local lists of dss_knn_points, self first; every
+ * cloud is treated as if it were alone; a list entry outside [0, P_n) is not followed; every packed slot of every given
+ * output is written by every call that launches, a slot that no cloud owns with (0,0,1) (as dss_local_frames does), stamp 0
+ * and parent -1, and nothing is read of it; a flip negates the three floats and changes nothing else; a repeated call
+ * returns the same bits.  P == 0 returns 0 without a launch.
+ *
+ * dss_disambiguate_normals: one thread per point, no workspace.
+ *   mode 0, the local rule (pytorch3d's and the reference's `_disambiguate_vector_directions`): K_n = min(K, P_n),
+ *     proj_j = (n.x dx + n.y dy) + n.z dz with d = q_j - p in fp32 over the first K_n list entries (an entry outside the
+ *     cloud counts as not positive); flip iff 2 #{proj_j > 0} < K_n.  viewpoint must be NULL.
+ *   mode 1, the viewpoint rule: flip iff (n.x vx + n.y vy) + n.z vz < 0 with v = viewpoint[n] - p; viewpoint (N,3);
+ *     knn_idx is not read and may be NULL.
+ *   Refusals: N < 1, P < 0 or P >= 2^31, K < 1, a mode other than 0 and 1, a viewpoint with mode 0 or none with mode 1, a
+ *   NULL pointer that the mode reads.
+ *
+ * dss_orient_normals: propagation of one sign over the neighbour lists.  KP_n = min(KP, K, P_n); the neighbours of i are the
+ * entries 1 .. KP_n - 1 of its list, an entry equal to i skipped.  tau = (0.95f, 0.8f, 0.5f, 0.0f).  State: level = 0,
+ * it = 0, every point unoriented.  While an unoriented point exists, it += 1 and
+ *   candidates: for an unoriented i and each neighbour j oriented in an EARLIER iteration,
+ *               d_ij = (n_i.x o_j.x + n_i.y o_j.y) + n_i.z o_j.z (n_i the input normal, o_j the output normal of j, fp32,
+ *               every operation rounded on its own); i is a candidate iff some |d_ij| >= tau[level] (a NaN never is);
+ *   round:      if a candidate exists, every candidate is oriented at once: its parent is the j of the largest |d_ij| among
+ *               those that pass, ties to the smallest id; o_i = d_ij < 0 ? -n_i : n_i; stamp[i] = it, parent[i] = j;
+ *               then level = 0;
+ *   level drop: else if level < 3: level += 1;
+ *   seed:       else the unoriented point with the largest z (ties to the smallest id; -0 equals +0; a NaN z loses to every
+ *               number; all NaN: the smallest id) is oriented: of (n.z, n.y, n.x) the first that is positive or negative
+ *               is made positive (none is: the normal stays); stamp = it, parent = -1, level = 0.
+ * Every iteration orients a point, drops a level or seeds, so the loop ends within 5 P_n iterations; the kernel carries that
+ * bound as a trip limit.  So stamp >= 1 everywhere in a cloud, the seeds are the points with parent -1, and following
+ * parents from any point reaches a seed through strictly decreasing stamps.
+ * normals_out (P,3) must not be normals_in; stamp (P,) int32 and parent (P,) int64 may be NULL.
+ * One workgroup per cloud for all of its iterations (grid = N): no atomics, no workgroup waits for another, one barrier per
+ * iteration (two in a seed iteration).  The stamps of a cloud of at most 40,000 points live in LDS; larger clouds keep them
+ * in `workspace`, slower and correct for any size.  The path is chosen per workgroup on the device from num_pts[n]; nothing
+ * is read back.  `workspace` (dss_orient_normals_workspace(N, P) bytes, never 0 for P > 0) also holds an int32 copy of the
+ * lists that a pass reads, 28 bytes a point, used when min(KP, K) <= 8; longer lists are read from knn_idx itself.
+ * Refusals (DSS_ERR_INVALID_ARGUMENT, nothing launched): N < 1, P < 0 or P > (2^31 - 1) / 5 (the largest stamp is an int),
+ * K < 1, KP < 1; a NULL pointer other than stamp / parent; normals_out == normals_in; a workspace smaller than the query
+ * says.
+ * ------------------------------------------------------------------------------------------- */
+DSS_API int dss_disambiguate_normals(const float *points /* (P,3) */, const float *normals_in /* (P,3) */,
+                                     const int64_t *knn_idx /* (P,K) */, const int64_t *first_idx, const int64_t *num_pts,
+                                     int N, int64_t P, int K, int mode, const float *viewpoint /* (N,3) or NULL */,
+                                     float *normals_out /* (P,3) */, void *stream);
+DSS_API size_t dss_orient_normals_workspace(int N, int64_t P);
+DSS_API int dss_orient_normals(const float *normals_in /* (P,3) */, const float *points /* (P,3) */,
+                               const int64_t *knn_idx /* (P,K) */, const int64_t *first_idx, const int64_t *num_pts,
+                               int N, int64_t P, int K, int KP, float *normals_out /* (P,3) */,
+                               int32_t *stamp /* (P,) or NULL */, int64_t *parent /* (P,) or NULL */, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Phong shading of the points = LightingTexture.forward (DSS/core/texture.py:65-125):
  * apply_lighting (:26-63) with lighting.py:10-77 (diffuse) and :80-172 (specular) for L PointLights
  * (point_lights = 1: light_vec = location, direction = location - point, lighting.py:239-302) or
