@@ -233,8 +233,9 @@ def test_cell_ordered_binning_of_large_inputs_is_exact(dist):
     Pc = len(pts)
     first = torch.tensor([0, Pc], dtype=torch.int64, device=DEV)
     num = torch.tensor([Pc, Pc - 1000], dtype=torch.int64, device=DEV)     # the last 1000 packed points belong to no cloud
+    feat0 = torch.rand((2 * Pc, 3), device=DEV)
     f = ops.render_forward(t(pts), t(nrm), torch.full((2,), float(h), device=DEV), t(M), t(V), torch.full((2,), 0.1, device=DEV),
-                           torch.full((2,), 100.0, device=DEV), first, num, torch.rand((2 * Pc, 3), device=DEV), S, K, 1.0, thr,
+                           torch.full((2,), 100.0, device=DEV), first, num, feat0, S, K, 1.0, thr,
                            1.0, False, True)
     want = ops.splat_points(f["pts_screen"], f["ellipse_params"], f["cutoff_threshold"], f["radii"], first, num, thr, S, K,
                             return_visible=True)
@@ -243,6 +244,9 @@ def test_cell_ordered_binning_of_large_inputs_is_exact(dist):
         assert float(want[3].mean()) < 1.0 / 16, "the far view is meant to cover a small part of the screen"
     for k, w_ in zip(("idx", "zbuf", "qvalue", "occupancy", "visible"), want):
         assert torch.equal(f[k], w_), (k, dist)
+    # the fused epilogue runs here from the records that the cell-ordered setup kernel wrote: the stand-alone blend's bits
+    img, wsum = ops.blend_forward(want[0], want[2], want[3], f["scaler"], feat0, return_wsum=True)
+    assert torch.equal(f["image"], img) and torch.equal(f["wsum"], wsum), dist
     # the workspace is left clean by the sorted path as well: a second call gives the same result
     f2 = ops.render_forward(t(pts), t(nrm), torch.full((2,), float(h), device=DEV), t(M), t(V), torch.full((2,), 0.1, device=DEV),
                             torch.full((2,), 100.0, device=DEV), first, num, torch.rand((2 * Pc, 3), device=DEV), S, K, 1.0, thr,
