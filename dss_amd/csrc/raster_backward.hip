@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "point_bodies.h"
+#include "cell_sort.h"
 
 namespace dss {
 
@@ -863,43 +864,22 @@ __global__ __launch_bounds__(PREP_THREADS) void band_filter_kernel(
 // the kernel was HBM-bound on re-reads.  A counting sort by (camera, 32 x 32-pixel cell) puts tasks that share rows next
 // to each other, and the gather deals whole runs of the sorted list to the same XCD (one L2).  The order of the tasks
 // does not change any result (every task writes only its own point).
+// The sort is the one of cell_sort.h (grid, key, LDS bookkeeping, column scan, scan of the cell totals: stated there, once
+// for this file and raster_forward.hip; with two atomic passes instead -- 2 x 2.4M global atomics -- it cost 0.45 ms, more
+// than it saves).  What is left here: the walk over the visible list whose length only the device knows (inactive
+// workgroups leave at once, the column scan covers the active blocks only, in one level), the band filter inside the
+// histogram pass and the scatter of the bare point ids.
 // ---------------------------------------------------------------------------------------------
-struct CellGrid {
-    int shift;      // cell side = 1 << shift pixels
-    int cx, cy;     // cells per image row / column
-    int total;      // N * cx * cy  (<= CELL_MAX: one LDS histogram)
-};
-#define CELL_MAX 16384          // 64 KB of LDS counters
-#define CELL_THREADS 1024
 #define CELL_PER_THREAD 16      // list entries per thread: a workgroup sorts 16384 entries
-#define CELL_CHUNK (CELL_THREADS * CELL_PER_THREAD)
-static CellGrid make_cells(int N, int S)
-{
-    CellGrid c;
-    c.shift = 5;   // 32 x 32-pixel cells (16 measures the same, 64 is 4 % slower)
-    for (;;) {
-        c.cx = ((S - 1) >> c.shift) + 1;
-        c.cy = c.cx;
-        c.total = N * c.cx * c.cy;
-        if (c.total <= CELL_MAX || c.shift >= 14) break;
-        ++c.shift;
-    }
-    return c;
-}
+#define CELL_CHUNK (CELL_SORT_THREADS * CELL_PER_THREAD)
 static inline size_t cell_blocks(int64_t P) { return (size_t)((P + CELL_CHUNK - 1) / CELL_CHUNK); }
 
-// A counting sort without global atomics (they run at ~16 G/s on this part: 2 x 2.4M of them cost 0.45 ms, more than the
-// sort saves): pass 1, per workgroup a histogram of its 16384 list entries in LDS -> block_hist[block][cell]; pass 2, a
-// thread per cell walks the active blocks (running sum = each block's first position within the cell) and one workgroup
-// scans the cell totals; pass 3, every workgroup ranks its entries again in LDS and writes them to
-// cell_start[cell] + block_base[block][cell] + rank.
 // Row band (multi-GPU, round 5): rs is known by now (median_final_kernel precedes this launch), so the entries that cannot
 // reach the rank's rows -- neither with their own box nor with the search window; the conservative test of
 // band_filter_kernel -- get no cell: they drop out of the sorted list the gather walks (at 8 ranks seven eighths of the
 // ~3.2M tasks of 8 x 1M points were rejected one by one inside the gather: 0.6 ms per rank and step for 0.16 ms of work) and
 // their zero partial sums are stored here.
-#define CELL_NONE 0xffffffffu
-__global__ __launch_bounds__(CELL_THREADS) void cell_hist_kernel(
+__global__ __launch_bounds__(CELL_SORT_THREADS) void cell_hist_kernel(
     const float *__restrict__ points, const int64_t *__restrict__ first_idx, const int64_t *__restrict__ num_pts, int N, int S,
     CellGrid cg, const uint32_t *__restrict__ vis_count, const int32_t *__restrict__ vis_list,
     uint32_t *__restrict__ cell_of, uint32_t *__restrict__ block_hist,
@@ -909,20 +889,16 @@ __global__ __launch_bounds__(CELL_THREADS) void cell_hist_kernel(
     extern __shared__ uint32_t s_hist[];
     const uint32_t count = *vis_count;
     const uint32_t b0 = blockIdx.x * (uint32_t)CELL_CHUNK;
-    if (b0 >= count) return;   // (inactive blocks: pass 2 never reads their rows)
-    for (int c = threadIdx.x; c < cg.total; c += CELL_THREADS) s_hist[c] = 0u;
-    __syncthreads();
+    if (b0 >= count) return;   // (inactive blocks: the column scan never reads their rows)
+    cell_hist_clear(s_hist, cg.total);
 #pragma unroll 4
     for (int u = 0; u < CELL_PER_THREAD; ++u) {
-        const uint32_t i = b0 + (uint32_t)u * CELL_THREADS + threadIdx.x;
+        const uint32_t i = b0 + (uint32_t)u * CELL_SORT_THREADS + threadIdx.x;
         if (i < count) {
             const int32_t p = vis_list[i];
             const int n = max(find_cloud(p, first_idx, num_pts, N), 0);
             const float px = points[3 * (size_t)p], py = points[3 * (size_t)p + 1];
-            // pixel column / row of the point (any monotone map of NDC does: only neighbourhood matters)
-            const float fx = (1.0f - px) * 0.5f * (float)S, fy = (1.0f - py) * 0.5f * (float)S;
-            const int ix = min(max((int)fx, 0), S - 1) >> cg.shift, iy = min(max((int)fy, 0), S - 1) >> cg.shift;
-            uint32_t key = (uint32_t)((n * cg.cy + iy) * cg.cx + ix);
+            uint32_t key = screen_cell(px, py, n, S, cg);
             if (radii) {
                 const int last_row = row0 + (((rows - 1) >> 3) << tshift) + ((rows - 1) & 7);
                 const float band_lo = -1 + (2 * (S - 1 - last_row)) / (float)S;     // lower edge of the lowest pixel row
@@ -934,17 +910,15 @@ __global__ __launch_bounds__(CELL_THREADS) void cell_hist_kernel(
                     in_band = ndc_index_range(py, reach, S, ylo, yhi) &&
                               band_row_ceil(S - 1 - yhi, row0, tshift) <= min(band_row_floor(S - 1 - ylo, row0, tshift), rows - 1);
                 }
-                if (!in_band) key = CELL_NONE;   // (its partial sums over this band are zero: visible_scan_kernel stored them)
+                if (!in_band) key = CELL_SORT_NONE;   // (its partial sums over this band are zero: visible_scan_kernel stored them)
             }
             cell_of[i] = key;
-            if (key != CELL_NONE) atomicAdd(&s_hist[key], 1u);
+            if (key != CELL_SORT_NONE) atomicAdd(&s_hist[key], 1u);
         }
     }
-    __syncthreads();
-    uint32_t *row = block_hist + (size_t)blockIdx.x * cg.total;
-    for (int c = threadIdx.x; c < cg.total; c += CELL_THREADS) row[c] = s_hist[c];
+    cell_hist_store(s_hist, cg.total, block_hist);
 }
-// thread per cell: block_hist[b][c] <- number of the cell's entries in blocks < b; cell_total[c]
+// thread per cell: block_hist[b][c] <- number of the cell's entries in the active blocks < b; cell_total[c]
 __global__ __launch_bounds__(256) void cell_block_scan_kernel(const uint32_t *__restrict__ vis_count, int total,
                                                               uint32_t *__restrict__ block_hist,
                                                               uint32_t *__restrict__ cell_total)
@@ -952,52 +926,14 @@ __global__ __launch_bounds__(256) void cell_block_scan_kernel(const uint32_t *__
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= total) return;
     const uint32_t nb = (*vis_count + (uint32_t)CELL_CHUNK - 1u) / (uint32_t)CELL_CHUNK;
-    uint32_t run = 0;
-    uint32_t b = 0;
-    // eight independent loads in flight per trip (one at a time the walk over ~150 blocks was 40 us of load latencies)
-    for (; b + 8 <= nb; b += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = block_hist[(size_t)(b + u) * total + c];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            block_hist[(size_t)(b + u) * total + c] = run;
-            run += v[u];
-        }
-    }
-    for (; b < nb; ++b) {
-        const uint32_t v = block_hist[(size_t)b * total + c];
-        block_hist[(size_t)b * total + c] = run;
-        run += v;
-    }
-    cell_total[c] = run;
+    cell_total[c] = cell_column_scan(block_hist, nb, total, c);
 }
-// one workgroup: exclusive scan of the cell totals -> cell_start
 __global__ __launch_bounds__(1024) void cell_scan_kernel(const uint32_t *__restrict__ cell_total, uint32_t *__restrict__ cell_start,
                                                          int total, uint32_t *__restrict__ sorted_count /* entries of the sorted list */)
 {
-    __shared__ uint32_t s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (total + 1023) / 1024;
-    const int b = tid * per, e = min(b + per, total);
-    uint32_t sum = 0;
-    for (int i = b; i < e; ++i) sum += cell_total[i];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = tid >= o ? s_part[tid - o] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
-    for (int i = b; i < e; ++i) {
-        cell_start[i] = run;
-        run += cell_total[i];
-    }
-    if (tid == 1023) *sorted_count = s_part[1023];
+    cell_start_scan(cell_total, cell_start, total, sorted_count);
 }
-__global__ __launch_bounds__(CELL_THREADS) void cell_scatter_kernel(
+__global__ __launch_bounds__(CELL_SORT_THREADS) void cell_scatter_kernel(
     CellGrid cg, const uint32_t *__restrict__ vis_count, const int32_t *__restrict__ vis_list,
     const uint32_t *__restrict__ cell_of, const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ block_base,
     int32_t *__restrict__ sorted)
@@ -1006,15 +942,13 @@ __global__ __launch_bounds__(CELL_THREADS) void cell_scatter_kernel(
     const uint32_t count = *vis_count;
     const uint32_t b0 = blockIdx.x * (uint32_t)CELL_CHUNK;
     if (b0 >= count) return;
-    const uint32_t *base = block_base + (size_t)blockIdx.x * cg.total;
-    for (int c = threadIdx.x; c < cg.total; c += CELL_THREADS) s_hist[c] = cell_start[c] + base[c];
-    __syncthreads();
+    cell_bases_load<false>(s_hist, cg.total, cell_start, block_base + (size_t)blockIdx.x * cg.total);
 #pragma unroll 4
     for (int u = 0; u < CELL_PER_THREAD; ++u) {
-        const uint32_t i = b0 + (uint32_t)u * CELL_THREADS + threadIdx.x;
+        const uint32_t i = b0 + (uint32_t)u * CELL_SORT_THREADS + threadIdx.x;
         if (i < count) {
             const uint32_t key = cell_of[i];
-            if (key != CELL_NONE) sorted[atomicAdd(&s_hist[key], 1u)] = vis_list[i];
+            if (key != CELL_SORT_NONE) sorted[atomicAdd(&s_hist[key], 1u)] = vis_list[i];
         }
     }
 }
@@ -2334,7 +2268,7 @@ static LongLayout long_layout(int N, int64_t P, int S)
 {
     LongLayout L;
     const size_t n = N > 0 ? N : 1, s = S > 0 ? S : 1, p = P > 0 ? (size_t)P : 1;
-    const size_t cells = (size_t)make_cells(N > 0 ? N : 1, S > 0 ? S : 1).total;
+    const size_t cells = (size_t)make_cell_grid(N > 0 ? N : 1, S > 0 ? S : 1, 0).total;
     size_t off = 0;
     L.hist = off;       L.vis_count = off + 3 * n * MED_BINS * 4;   // histograms, then the list lengths (unsorted, sorted)
     off += align_up(3 * n * MED_BINS * 4 + 256, 256);
@@ -2743,7 +2677,7 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
                                rs, first_idx, num_pts, N, S, row0, rows, vis_count, vis_list, grad_pts, grad_feat, C, tshift, own);
     } else {
         const LongLayout L = long_layout(N, P, S);
-        const CellGrid cg = make_cells(N, S);
+        const CellGrid cg = make_cell_grid(N, S, 0);
         uint32_t *hist = reinterpret_cast<uint32_t *>(w + L.hist);
         vis_count = reinterpret_cast<uint32_t *>(w + L.vis_count);
         int32_t *unsorted = reinterpret_cast<int32_t *>(w + L.vis_list);
@@ -2775,12 +2709,12 @@ static int render_backward_impl(bool run_prep, const float *grad_out, const int3
             const unsigned cb = (unsigned)cell_blocks(P);   // (the visible count is only known on the device: P bounds it)
             const size_t lds = (size_t)cg.total * 4;
             // (row band: the entries that cannot reach it drop out of the sorted list)
-            hipLaunchKernelGGL(cell_hist_kernel, dim3(cb), dim3(CELL_THREADS), lds, st, points, first_idx, num_pts, N, S, cg,
+            hipLaunchKernelGGL(cell_hist_kernel, dim3(cb), dim3(CELL_SORT_THREADS), lds, st, points, first_idx, num_pts, N, S, cg,
                                vis_count, unsorted, cell_of, block_hist, band ? radii : nullptr, rs, row0, rows, tshift, own);
             hipLaunchKernelGGL(cell_block_scan_kernel, dim3((unsigned)((cg.total + 255) / 256)), dim3(256), 0, st, vis_count,
                                cg.total, block_hist, cell_total);
             hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, cell_total, cell_start, cg.total, vis_count + 1);
-            hipLaunchKernelGGL(cell_scatter_kernel, dim3(cb), dim3(CELL_THREADS), lds, st, cg, vis_count, unsorted, cell_of,
+            hipLaunchKernelGGL(cell_scatter_kernel, dim3(cb), dim3(CELL_SORT_THREADS), lds, st, cg, vis_count, unsorted, cell_of,
                                cell_start, block_hist, sorted);
         }
         if (own && !own_given) { OW.alpha = plane; OW.astride = 1; }

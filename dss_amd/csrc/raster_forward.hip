@@ -28,6 +28,7 @@ namespace dss { extern __device__ long long *g_fine_timing; }
     } while (0)
 #endif
 #include "setup_body.h"
+#include "cell_sort.h"
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
@@ -479,12 +480,13 @@ __global__ __launch_bounds__(256) void spill_kernel(
 // 4-byte list appends that each dirty their own 64-byte sector (1.7 GB written for 0.9 GB of output) and 0.4 ms of
 // returning global atomics (~2.2 per splat at ~16 G/s) -- measured by removing each in turn.  A cloud in Morton order pays
 // 0.65 ms for the same work, because neighbouring threads then append to the same few lists.  Here the renderer creates
-// that order itself, without global atomics:
-//   setup_cell_kernel   per-point setup (same body) + the 32 x 32-pixel screen cell of every splat's centre + a histogram
-//                       of the workgroup's 16,384 splats in LDS -> block_hist[block][cell]
-//   sort_block_scan / sort_seg_scan / sort_cell_scan   exclusive prefix of every cell over the blocks (two levels), of the
-//                       cells over the image
-//   sort_scatter_kernel every workgroup ranks its splats again in LDS and writes (px, py, rx, ry | id) in cell order
+// that order itself, with the counting sort by screen cell of cell_sort.h (the grid, the key, the LDS bookkeeping, the
+// column scan and the scan of the cell totals are stated there, once for this file and raster_backward.hip).  What is left
+// here is the forward's own:
+//   setup_cell_kernel   step 1 around the per-point setup (same body as setup_bin_kernel): which splats get a cell, the
+//                       extra cell of the culled ones, the reuse form that does not sort at all
+//   sort_block_scan / sort_seg_scan / sort_cell_scan   steps 2 and 3, step 2 in two levels (segments of SORT_SEG blocks)
+//   sort_scatter_kernel step 4: the record (px, py, rx, ry | ellipse, pz), the id and the inverse order of every splat
 //   bin_sorted_kernel   1024 consecutive sorted splats per workgroup -- one or two cells -- : the (tile, sub-list) keys of
 //                       their pairs are counted in an LDS hash table, ONE global atomicAdd per key reserves the run, the
 //                       ids are written behind it: ~8x fewer global atomics, list appends in contiguous runs
@@ -499,38 +501,18 @@ __global__ __launch_bounds__(256) void spill_kernel(
 #ifndef SORT_MIN_P               // (-DSORT_MIN_P=...: development A/B builds, tools/ab_bench.py)
 #define SORT_MIN_P 2000000      // below ~2M splats the direct binning wins (8 x 99,790 points: 0.69 vs 0.73 ms per step)
 #endif
-#define SORT_THREADS 1024
-#define SORT_PER_THREAD 16                            // at most: 16,384 splats per workgroup of the histogram pass
-#define SORT_CELL_MAX 16384                           // 64 KB of LDS counters
-#define SORT_NO_CELL 0xffffffffu
-struct SortGrid {
-    int shift;     // cell side = 1 << shift pixels
-    int cx, cy;    // cells per image row / column
-    int total;     // N * cx * cy + 1 (<= SORT_CELL_MAX)
-};
-static SortGrid make_sort_grid(int N, int S)
-{
-    SortGrid c;
-    c.shift = 5;
-    for (;;) {
-        c.cx = ((S - 1) >> c.shift) + 1;
-        c.cy = c.cx;
-        c.total = N * c.cx * c.cy + 1;   // + the cell of the culled splats (last; only filled when the order is saved)
-        if (c.total <= SORT_CELL_MAX || c.shift >= 14) break;
-        ++c.shift;
-    }
-    return c;
-}
+#define SORT_PER_THREAD 16      // at most: 16,384 splats per workgroup of the histogram pass
+#define SORT_EXTRA_CELLS 1      // make_cell_grid: the cell of the culled splats (last; only filled when the order is saved)
 // splats per thread of the histogram pass: at least ~2 workgroups per CU (49 workgroups of 16,384 splats left four fifths of
 // the chip idle at 8 x 99,790 points), at most SORT_PER_THREAD
 static inline int sort_per_thread(int64_t P)
 {
-    int64_t per = P / ((int64_t)SORT_THREADS * 512);
+    int64_t per = P / ((int64_t)CELL_SORT_THREADS * 512);
     return (int)(per < 1 ? 1 : (per > SORT_PER_THREAD ? SORT_PER_THREAD : per));
 }
 static inline size_t sort_blocks(int64_t P)
 {
-    const int64_t chunk = (int64_t)SORT_THREADS * sort_per_thread(P);
+    const int64_t chunk = (int64_t)CELL_SORT_THREADS * sort_per_thread(P);
     return (size_t)((P + chunk - 1) / chunk);
 }
 // MODE 0: the order of this call only (culled splats are left out).  MODE 1 (DSS_WS_ORDER_SAVE): culled splats are sorted
@@ -538,7 +520,7 @@ static inline size_t sort_blocks(int64_t P)
 // MODE 2 (DSS_WS_ORDER_REUSE): no histogram at all -- the setup alone, plus the 16-byte binning record (px, py, rx, ry) of
 // every point in NATURAL order (rx = -1: culled) that bin_sorted_kernel<true> gathers through the saved order.
 template <int MODE>
-__global__ __launch_bounds__(SORT_THREADS) void setup_cell_kernel(const SetupArgs A, SortGrid sg, int per_thread,
+__global__ __launch_bounds__(CELL_SORT_THREADS) void setup_cell_kernel(const SetupArgs A, CellGrid sg, int per_thread,
                                                                    uint32_t *__restrict__ cell_of,
                                                                    uint32_t *__restrict__ block_hist, Spill sp,
                                                                    uint8_t *__restrict__ visible_to_clear,
@@ -552,11 +534,8 @@ __global__ __launch_bounds__(SORT_THREADS) void setup_cell_kernel(const SetupArg
     // ~140 bytes a splat writes here seven eighths of the cloud keep 38
     extern __shared__ uint32_t s_hist[];
     if (sp.ctrl && blockIdx.x == 0 && threadIdx.x == 0) spill_begin(sp);
-    if (MODE != 2) {
-        for (int c = threadIdx.x; c < sg.total; c += SORT_THREADS) s_hist[c] = 0u;
-        __syncthreads();
-    }
-    const int64_t b0 = (int64_t)blockIdx.x * (MODE == 2 ? (int)blockDim.x : SORT_THREADS) * per_thread;
+    if (MODE != 2) cell_hist_clear(s_hist, sg.total);
+    const int64_t b0 = (int64_t)blockIdx.x * (MODE == 2 ? (int)blockDim.x : CELL_SORT_THREADS) * per_thread;
     if (MODE == 2) {
         // this kernel is nothing but streaming stores (~140 bytes per point): full wavefronts write them as contiguous runs
         // (setup_wave_store; the dynamic LDS of this instantiation is 4 KB per wavefront)
@@ -630,7 +609,7 @@ __global__ __launch_bounds__(SORT_THREADS) void setup_cell_kernel(const SetupArg
     }
 #pragma unroll 1
     for (int u = 0; u < per_thread; ++u) {
-        const int64_t p = b0 + (int64_t)u * SORT_THREADS + threadIdx.x;
+        const int64_t p = b0 + (int64_t)u * CELL_SORT_THREADS + threadIdx.x;
         if (p >= A.P) break;
         if (visible_to_clear) visible_to_clear[p] = 0;
         const int n = find_cloud(p, A.first_idx, A.num_pts, A.N);
@@ -647,26 +626,19 @@ __global__ __launch_bounds__(SORT_THREADS) void setup_cell_kernel(const SetupArg
         }
         // culled splats (pz = -1) never reach a tile list; band_only, MODE 0: neither do the splats that miss the band
         const bool live = n >= 0 && !(pz < 0) && (MODE == 1 || reach);
-        uint32_t key = SORT_NO_CELL;
-        if (live) {
-            // pixel column / row of the centre (any monotone map of NDC does: only neighbourhood matters); NaN -> cell 0
-            const float fx = (1.0f - px) * 0.5f * (float)A.S, fy = (1.0f - py) * 0.5f * (float)A.S;
-            const int ix = min(max((int)fx, 0), A.S - 1) >> sg.shift, iy = min(max((int)fy, 0), A.S - 1) >> sg.shift;
-            key = (uint32_t)((n * sg.cy + iy) * sg.cx + ix);
-        } else if (MODE == 1) {
-            key = (uint32_t)(sg.total - 1);
-        }
-        if (key != SORT_NO_CELL) atomicAdd(&s_hist[key], 1u);
+        uint32_t key = CELL_SORT_NONE;
+        if (live) key = screen_cell(px, py, n, A.S, sg);   // (NaN -> cell 0)
+        else if (MODE == 1) key = (uint32_t)(sg.total - 1);
+        if (key != CELL_SORT_NONE) atomicAdd(&s_hist[key], 1u);
         cell_of[p] = key;
     }
-    __syncthreads();
-    uint32_t *row = block_hist + (size_t)blockIdx.x * sg.total;
-    for (int c = threadIdx.x; c < sg.total; c += SORT_THREADS) row[c] = s_hist[c];
+    cell_hist_store(s_hist, sg.total, block_hist);
 }
 // Prefix of every cell over the blocks, two levels (one thread per cell walking 500+ blocks was 36-39 us of load latency):
 // sort_block_scan_kernel, grid (cells / 256, segments of SORT_SEG blocks): block_hist[b][c] <- the cell's splats in the
-// earlier blocks of b's segment, seg_tot[seg][c] <- the segment's total; sort_seg_scan_kernel, one thread per cell:
-// seg_tot[seg][c] <- the cell's splats in earlier segments, cell_total[c].
+// earlier blocks of b's segment, seg_tot[seg][c] <- the segment's total (the column scan of cell_sort.h over one segment,
+// fully unrolled); sort_seg_scan_kernel, one thread per cell: seg_tot[seg][c] <- the cell's splats in earlier segments,
+// cell_total[c].  sort_cell_scan_kernel: step 3.
 #define SORT_SEG 8
 __global__ __launch_bounds__(256) void sort_block_scan_kernel(uint32_t nb, int total, uint32_t *__restrict__ block_hist,
                                                               uint32_t *__restrict__ seg_tot)
@@ -689,69 +661,30 @@ __global__ __launch_bounds__(256) void sort_seg_scan_kernel(uint32_t nseg, int t
                                                             uint32_t *__restrict__ cell_total)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= total) return;
-    uint32_t run = 0, sg = 0;
-    for (; sg + 8 <= nseg; sg += 8) {   // eight independent loads in flight per trip
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = seg_tot[(size_t)(sg + u) * total + c];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            seg_tot[(size_t)(sg + u) * total + c] = run;
-            run += v[u];
-        }
-    }
-    for (; sg < nseg; ++sg) {
-        const uint32_t v = seg_tot[(size_t)sg * total + c];
-        seg_tot[(size_t)sg * total + c] = run;
-        run += v;
-    }
-    cell_total[c] = run;
+    if (c < total) cell_total[c] = cell_column_scan(seg_tot, nseg, total, c);
 }
-// one workgroup: exclusive scan of the cell totals -> cell_start; the number of sorted splats -> *sorted_count
 __global__ __launch_bounds__(1024) void sort_cell_scan_kernel(const uint32_t *__restrict__ cell_total, uint32_t *__restrict__ cell_start,
                                                               int total, uint32_t *__restrict__ sorted_count)
 {
-    __shared__ uint32_t s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (total + 1023) / 1024;
-    const int b = tid * per, e = min(b + per, total);
-    uint32_t sum = 0;
-    for (int i = b; i < e; ++i) sum += cell_total[i];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = tid >= o ? s_part[tid - o] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
-    for (int i = b; i < e; ++i) {
-        cell_start[i] = run;
-        run += cell_total[i];
-    }
-    if (tid == 1023) *sorted_count = s_part[1023];
+    cell_start_scan(cell_total, cell_start, total, sorted_count);
 }
-__global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(
-    const float *__restrict__ points, const float *__restrict__ radii, const float *__restrict__ ellipse, int64_t P, SortGrid sg,
+__global__ __launch_bounds__(CELL_SORT_THREADS) void sort_scatter_kernel(
+    const float *__restrict__ points, const float *__restrict__ radii, const float *__restrict__ ellipse, int64_t P, CellGrid sg,
     int per_thread, const uint32_t *__restrict__ cell_of,
     const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ block_base, const uint32_t *__restrict__ seg_base,
     float4 *__restrict__ crec, int32_t *__restrict__ s_id, int32_t *__restrict__ inv /* saved order only, else nullptr */)
 {
     extern __shared__ uint32_t s_hist[];
     // (merging two or four histogram blocks per scatter workgroup -- longer runs per cell -- measured 2-4 % slower)
-    const uint32_t *base = block_base + (size_t)blockIdx.x * sg.total;
-    const uint32_t *sbase = seg_base + (size_t)(blockIdx.x / SORT_SEG) * sg.total;
-    for (int c = threadIdx.x; c < sg.total; c += SORT_THREADS) s_hist[c] = cell_start[c] + sbase[c] + base[c];
-    __syncthreads();
-    const int64_t b0 = (int64_t)blockIdx.x * SORT_THREADS * per_thread;
+    cell_bases_load<true>(s_hist, sg.total, cell_start, block_base + (size_t)blockIdx.x * sg.total,
+                          seg_base + (size_t)(blockIdx.x / SORT_SEG) * sg.total);
+    const int64_t b0 = (int64_t)blockIdx.x * CELL_SORT_THREADS * per_thread;
 #pragma unroll 4
     for (int u = 0; u < per_thread; ++u) {
-        const int64_t p = b0 + (int64_t)u * SORT_THREADS + threadIdx.x;
+        const int64_t p = b0 + (int64_t)u * CELL_SORT_THREADS + threadIdx.x;
         if (p >= P) break;
         const uint32_t key = cell_of[p];
-        if (key == SORT_NO_CELL) continue;
+        if (key == CELL_SORT_NONE) continue;
         const float2 rr = reinterpret_cast<const float2 *>(radii)[p];
         // (the last cell only receives splats when the order is saved: the culled ones, rx = -1 for the binning)
         const float4 ge = make_float4(points[3 * p], points[3 * p + 1], key == (uint32_t)(sg.total - 1) ? -1.0f : rr.x, rr.y);
@@ -1998,7 +1931,7 @@ struct FwdWorkspace {
     Spill spill;
     float4 *rec;         // packed splat records (P x 64 bytes) behind the lists; only carved for the fused forward
     // cell-ordered binning (fused forward, P > SORT_MIN_P; nullptr otherwise): every region is fully rewritten per call
-    uint32_t *sort_cell_of;      // (P) cell of every splat, SORT_NO_CELL for culled ones
+    uint32_t *sort_cell_of;      // (P) cell of every splat, CELL_SORT_NONE for culled ones
     uint32_t *sort_block_hist;   // (blocks, cells) per-block histogram, then per-block offsets
     uint32_t *sort_cell_total, *sort_cell_start;   // (cells)
     uint32_t *sort_seg_tot;      // (segments of SORT_SEG blocks, cells)
@@ -2090,7 +2023,7 @@ static FwdWorkspace carve_fwd(void *ws, int N, int64_t P, int S, bool with_recor
     w.spill.fail = b.take<uint32_t>(64);                // 256-byte block, never zeroed (see Spill::fail)
     if (with_records && !lean) w.rec = b.take<float4>(np * 4);
     if (with_records && !lean && P > SORT_MIN_P) {
-        const SortGrid sg = make_sort_grid(N, S);
+        const CellGrid sg = make_cell_grid(N, S, SORT_EXTRA_CELLS);
         const size_t blocks = sort_blocks(P);
         w.sort_cell_of = b.take<uint32_t>(np);
         w.sort_block_hist = b.take<uint32_t>(blocks * (size_t)sg.total);
@@ -2379,7 +2312,7 @@ static int bin_cell_ordered(const SetupArgs &SA, const FwdWorkspace &w, const Ti
 {
     const int N = SA.N, tiles = g.tiles_x * g.tiles_y;
     const int64_t P = SA.P;
-    const SortGrid sg = make_sort_grid(N, SA.S);
+    const CellGrid sg = make_cell_grid(N, SA.S, SORT_EXTRA_CELLS);
     const unsigned bin_wgs = (unsigned)((P + SORT_BIN_CHUNK - 1) / SORT_BIN_CHUNK);
     if (s.order == ORDER_REUSE) {
         // the point order an earlier call left in the workspace: setup in natural order + one gathered binning pass
@@ -2399,7 +2332,7 @@ static int bin_cell_ordered(const SetupArgs &SA, const FwdWorkspace &w, const Ti
         const size_t lds = (size_t)sg.total * 4;
         // (the position bytes of the band ranks' binning start lowered with every saved order)
         if (save && hipMemsetAsync(w.sort_live, 0, (size_t)P, st) != hipSuccess) return check_launch("dss_render_forward (order bytes)");
-        hipLaunchKernelGGL((save ? setup_cell_kernel<ORDER_SAVE> : setup_cell_kernel<ORDER_NONE>), dim3(sb), dim3(SORT_THREADS), lds,
+        hipLaunchKernelGGL((save ? setup_cell_kernel<ORDER_SAVE> : setup_cell_kernel<ORDER_NONE>), dim3(sb), dim3(CELL_SORT_THREADS), lds,
                            st, SA, sg, per, w.sort_cell_of, w.sort_block_hist, w.spill, visible, w.sort_crec, w.sort_inv, g,
                            s.band_only, (uint8_t *)nullptr);
         hipLaunchKernelGGL(sort_block_scan_kernel, dim3((unsigned)((sg.total + 255) / 256), nseg), dim3(256), 0, st, sb,
@@ -2408,7 +2341,7 @@ static int bin_cell_ordered(const SetupArgs &SA, const FwdWorkspace &w, const Ti
                            w.sort_seg_tot, w.sort_cell_total);
         hipLaunchKernelGGL(sort_cell_scan_kernel, dim3(1), dim3(1024), 0, st, w.sort_cell_total, w.sort_cell_start, sg.total,
                            w.sort_count);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3(sb), dim3(SORT_THREADS), lds, st, SA.screen, SA.radii, SA.ellipse, P, sg, per,
+        hipLaunchKernelGGL(sort_scatter_kernel, dim3(sb), dim3(CELL_SORT_THREADS), lds, st, SA.screen, SA.radii, SA.ellipse, P, sg, per,
                            w.sort_cell_of, w.sort_cell_start, w.sort_block_hist, w.sort_seg_tot, w.sort_crec, w.sort_id,
                            save ? w.sort_inv : (int32_t *)nullptr);
         hipLaunchKernelGGL(bin_sorted_kernel<false>, dim3(bin_wgs), dim3(SORT_BIN_THREADS), 0, st, w.sort_crec, w.sort_id,
