@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "point_bodies.h"
 #include "cell_sort.h"
+#include "backward_prep.h"
 
 namespace dss {
 
@@ -35,52 +36,19 @@ __device__ __forceinline__ float key_float(uint32_t k)
 #define MED_BINS 2048
 #define MED_PTS_PER_WG 2048
 
-// Rank-k selection in a 2048-bin histogram (global or LDS) by one 256-thread workgroup:
-// returns the bin that holds rank k and the rank inside that bin (uniform across the workgroup).
-// If total_out != nullptr the sum of all bins is stored there.
+// Rank-k selection in a 2048-bin histogram in global memory by one 256-thread workgroup (rank_select, backward_prep.h):
+// the bin that holds rank k, the rank inside that bin and the sum of all bins, uniform across the workgroup.
 __device__ __forceinline__ void select_bin(const uint32_t *hist, uint32_t k, bool k_is_lower_median,
-                                           uint32_t *s_scan /*[4+3]*/, uint32_t &bin_out, uint32_t &k_out,
+                                           uint32_t *s_scan /*[4+2]*/, uint32_t &bin_out, uint32_t &k_out,
                                            uint32_t &total_out)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     uint32_t h[8];
-    uint32_t v = 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        h[i] = hist[8 * tid + i];
-        v += h[i];
-    }
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    __syncthreads();  // s_scan reuse
-    if (lane == 63) s_scan[wid] = x;
-    __syncthreads();
-    uint32_t woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < MED_THREADS / 64; ++w) {
-        if (w < wid) woff += s_scan[w];
-        total += s_scan[w];
-    }
-    if (k_is_lower_median) k = (total > 0) ? (total - 1) / 2 : 0;  // torch.median = lower median
-    uint32_t excl = woff + x - v;
-    if (total > 0 && k >= excl && k < excl + v) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (k >= excl && k < excl + h[i]) {
-                s_scan[4] = 8 * tid + i;
-                s_scan[5] = k - excl;
-            }
-            excl += h[i];
-        }
-    }
-    __syncthreads();
-    bin_out = s_scan[4];
-    k_out = s_scan[5];
-    total_out = total;
+    for (int i = 0; i < 8; ++i) h[i] = hist[8 * threadIdx.x + i];
+    const RankBin r = rank_select<MED_THREADS, 8>(h, 8u * threadIdx.x, k, k_is_lower_median, s_scan);
+    bin_out = r.bin;
+    k_out = r.k;
+    total_out = r.total;
 }
 
 // digits of the order-preserving key: bits [31:21], [20:10], [9:0]
@@ -307,9 +275,9 @@ __global__ __launch_bounds__(MED_THREADS) void visible_scan_kernel(
     uint32_t wave_cnt = 0;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
-        const unsigned long long m = __ballot(vis[u] != 0);
-        rank[u] = wave_cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        wave_cnt += (uint32_t)__popcll(m);
+        uint32_t cnt;
+        rank[u] = wave_cnt + lane_rank(vis[u] != 0, cnt);
+        wave_cnt += cnt;
     }
     if (lane == 0) s_wave[wid] = wave_cnt;
     for (int i = tid; i < MED_BINS; i += MED_THREADS) lh[i] = 0;
@@ -326,11 +294,7 @@ __global__ __launch_bounds__(MED_THREADS) void visible_scan_kernel(
     for (int u = 0; u < PER; ++u) {
         const int64_t i = c0 + tid + (int64_t)u * MED_THREADS;
         if (vis[u]) vis_list[base + rank[u]] = (int32_t)i;
-        if ((!vis[u] || zero_all) && i < c1) {
-            grad_pts[3 * i] = 0.0f; grad_pts[3 * i + 1] = 0.0f; grad_pts[3 * i + 2] = 0.0f;
-            if (grad_feat)
-                for (int ch = 0; ch < C; ++ch) grad_feat[(size_t)i * C + ch] = 0.0f;
-        }
+        if ((!vis[u] || zero_all) && i < c1) zero_grad_rows(grad_pts, grad_feat, C, (size_t)i);
     }
     // ---- radix-select pass 0 (digit [31:21]) per cloud overlapping this chunk ----
     for (int n = 0; n < N; ++n) {
@@ -377,6 +341,8 @@ __global__ __launch_bounds__(MED_THREADS) void visible_scan_kernel(
 // CUs, single-CU work only on the visible ~40 %.
 // Pass-0 histograms are replicated 32x by lane (address = bin * 32 + lane % 32): screen-space radii share one
 // or two exponent bytes and same-address LDS atomics serialise.
+// The ordered ranks of a segment, the span of a cloud inside it, the zero rows and the rank-k selection are bodies of
+// backward_prep.h, shared with the long-list kernels above and the fused form below.
 // ---------------------------------------------------------------------------------------------
 #define PREP_THREADS 1024
 #define PREP_MAX_SEG 64          // segments a wavefront can scan in registers
@@ -402,24 +368,6 @@ static inline int prep_points_per_thread(int64_t P)
 #define PREP_MARK(slot)
 #endif
 
-// Wave-wide inclusive scan on the VALU (DPP row shifts + row broadcasts; `__shfl_up` would be six dependent
-// ds_bpermute round trips).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_u32_zero(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    v += dpp_u32_zero<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_u32_zero<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_u32_zero<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_u32_zero<0x118, 0xf>(v);  // row_shr:8  -> inclusive scan inside each row of 16
-    v += dpp_u32_zero<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v += dpp_u32_zero<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
 // Sum of the 32 lane-replicas of bin (tid >> 2), valid in the lanes with (tid & 3) == 0 (others return 0).
 __device__ __forceinline__ uint32_t replica_sum_256(const uint32_t *lh)
 {
@@ -432,42 +380,6 @@ __device__ __forceinline__ uint32_t replica_sum_256(const uint32_t *lh)
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);  // quad_perm [2,3,0,1]
     return q == 0 ? v : 0u;
-}
-
-// Rank-k selection by a 1024-thread workgroup: thread owns bins first_bin .. first_bin + 3 with counts h[].
-__device__ __forceinline__ void block_select(const uint32_t (&h)[4], uint32_t first_bin, uint32_t k,
-                                             bool k_is_lower_median, uint32_t *s_w /*[16]*/, uint32_t *s_sel /*[2]*/,
-                                             uint32_t &bin_out, uint32_t &k_out, uint32_t &total_out)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const uint32_t v = (h[0] + h[1]) + (h[2] + h[3]);
-    const uint32_t x = wave_incl_scan(v);
-    __syncthreads();  // s_w / s_sel reuse
-    if (lane == 63) s_w[wid] = x;
-    __syncthreads();
-    uint32_t woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < PREP_THREADS / 64; ++w) {
-        const uint32_t c = s_w[w];
-        if (w < wid) woff += c;
-        total += c;
-    }
-    if (k_is_lower_median) k = (total > 0) ? (total - 1) / 2 : 0;  // torch.median = lower median
-    uint32_t excl = woff + x - v;
-    if (total > 0 && k >= excl && k < excl + v) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (k >= excl && k < excl + h[i]) {
-                s_sel[0] = first_bin + i;
-                s_sel[1] = k - excl;
-            }
-            excl += h[i];
-        }
-    }
-    __syncthreads();
-    bin_out = s_sel[0];
-    k_out = s_sel[1];
-    total_out = total;
 }
 
 // Dense copy of the alpha channel of the image gradient: plane[i] = grad_out[i * (C + 1) + C].
@@ -507,7 +419,7 @@ __global__ __launch_bounds__(PREP_THREADS) void backward_compact_kernel(
     __shared__ uint32_t lh[256 * 32];
     __shared__ uint32_t s_w[PER * PREP_THREADS / 64];
     __shared__ uint32_t s_rng[2];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const unsigned chunk = blockIdx.x;
     const int64_t c0 = (int64_t)chunk * PREP_CHUNK;
     const int64_t c1 = min(c0 + PREP_CHUNK, P);
@@ -536,25 +448,7 @@ __global__ __launch_bounds__(PREP_THREADS) void backward_compact_kernel(
     // order-preserving ranks (entries of a segment are sorted by point id, so the entries of one cloud are a
     // contiguous range of it): rank = visible points before (u, wave, lane) in that order
     uint32_t rank[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const unsigned long long m = __ballot((vmask >> u) & 1u);
-        rank[u] = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (lane == 0) s_w[u * (PREP_THREADS / 64) + wid] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    uint32_t tot = 0;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        uint32_t before = tot;
-#pragma unroll
-        for (int w = 0; w < PREP_THREADS / 64; ++w) {
-            const uint32_t c = s_w[u * (PREP_THREADS / 64) + w];
-            if (w < wid) before += c;
-            tot += c;
-        }
-        rank[u] += before;
-    }
+    const uint32_t tot = ordered_ranks<PER, PREP_THREADS>(vmask, rank, s_w);
     if (tid == 0) seg_count[chunk] = tot;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
@@ -563,9 +457,7 @@ __global__ __launch_bounds__(PREP_THREADS) void backward_compact_kernel(
             vis_list[c0 + rank[u]] = (int32_t)i;
             vis_keys[c0 + rank[u]] = kk[u];
         } else if (i < c1 && grad_pts) {
-            grad_pts[3 * i] = 0.0f; grad_pts[3 * i + 1] = 0.0f; grad_pts[3 * i + 2] = 0.0f;
-            if (grad_feat)
-                for (int ch = 0; ch < C; ++ch) grad_feat[(size_t)i * C + ch] = 0.0f;
+            zero_grad_rows(grad_pts, grad_feat, C, (size_t)i);
         }
     }
     // pass-0 histogram of this chunk, one per cloud that overlaps it (normally one)
@@ -577,14 +469,7 @@ __global__ __launch_bounds__(PREP_THREADS) void backward_compact_kernel(
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int64_t i = c0 + tid + (int64_t)u * PREP_THREADS;
-            const bool vis_u = (vmask >> u) & 1u;
-            const bool mine = vis_u && i >= lo && i < hi;
-            const unsigned long long mb = __ballot(vis_u && i < lo), mi = __ballot(mine);
-            if (lane == 0) {
-                if (mb) atomicAdd(&s_rng[0], (uint32_t)__popcll(mb));
-                if (mi) atomicAdd(&s_rng[1], (uint32_t)__popcll(mi));
-            }
-            if (mine) {
+            if (cloud_span_step((vmask >> u) & 1u, i, lo, hi, s_rng)) {
                 atomicAdd(&lh[(kk[u].x >> 24) * 32 + (lane & 31)], 1u);
                 atomicAdd(&lh[(kk[u].y >> 24) * 32 + (lane & 31)], 1u);
             }
@@ -607,8 +492,7 @@ __global__ __launch_bounds__(PREP_THREADS) void median_visible_kernel(
     float radii_s, float *__restrict__ rs)
 {
     __shared__ uint32_t lh[4096];
-    __shared__ uint32_t s_w[PREP_THREADS / 64];
-    __shared__ uint32_t s_sel[2];
+    __shared__ uint32_t s_sel[PREP_THREADS / 64 + 2];   // scratch of rank_select
     const int tid = threadIdx.x, lane = tid & 63;
     const int n = blockIdx.x;
     const int64_t f = first_idx[n];
@@ -665,9 +549,10 @@ __global__ __launch_bounds__(PREP_THREADS) void median_visible_kernel(
         hv += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hv, 0xB1, 0xf, 0xf, true);
         hv += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hv, 0x4E, 0xf, 0xf, true);
         const uint32_t h[4] = {hq == 0 ? hv : 0u, 0u, 0u, 0u};
-        uint32_t bin;
-        block_select(h, (uint32_t)hb, 0u, true, s_w, s_sel, bin, k, total0);
-        prefix = bin << 24;
+        const RankBin r = rank_select<PREP_THREADS, 4>(h, (uint32_t)hb, 0u, true, s_sel);
+        k = r.k;
+        total0 = r.total;
+        prefix = r.bin << 24;
         pmask = 0xff000000u;
     }
     PREP_MARK(7);
@@ -705,9 +590,9 @@ __global__ __launch_bounds__(PREP_THREADS) void median_visible_kernel(
         asm volatile("" : "+v"(t4));
         const uint4 q = reinterpret_cast<const uint4 *>(lh)[t4];
         const uint32_t h[4] = {q.x, q.y, q.z, q.w};
-        uint32_t bin, tot;
-        block_select(h, 4u * tid, k, false, s_w, s_sel, bin, k, tot);
-        prefix |= bin << sh;
+        const RankBin r = rank_select<PREP_THREADS, 4>(h, 4u * tid, k, false, s_sel);
+        k = r.k;
+        prefix |= r.bin << sh;
         pmask |= 0xfffu << sh;
         __syncthreads();  // lh is re-zeroed by the next pass
         PREP_MARK(7 + 2 * pass);
@@ -715,34 +600,7 @@ __global__ __launch_bounds__(PREP_THREADS) void median_visible_kernel(
     if (tid == 0) rs[n] = key_float(prefix) * radii_s;
 }
 
-// Band-local row <-> image row of a (possibly tile-row-cyclic) band, see TileGrid::tshift in raster_forward.hip:
-// image row of band row l = row0 + ((l >> 3) << tshift) + (l & 7); contiguous band: tshift = 3, i.e. row0 + l.
-__device__ __forceinline__ int band_image_row(int l, int row0, int tshift) { return row0 + ((l >> 3) << tshift) + (l & 7); }
-// smallest band row whose image row is >= r (may equal `rows`: none)
-__device__ __forceinline__ int band_row_ceil(int r, int row0, int tshift)
-{
-    const int x = r - row0;
-    if (x <= 0) return 0;
-    const int q = x >> tshift, m = x & ((1 << tshift) - 1);
-    return m < 8 ? 8 * q + m : 8 * (q + 1);
-}
-// largest band row whose image row is <= r (-1: none)
-__device__ __forceinline__ int band_row_floor(int r, int row0, int tshift)
-{
-    const int x = r - row0;
-    if (x < 0) return -1;
-    const int q = x >> tshift, m = x & ((1 << tshift) - 1);
-    return 8 * q + min(m, 7);
-}
-
-// is image row r one of the band's rows?
-__device__ __forceinline__ bool band_owns_row(int r, int row0, int rows, int tshift)
-{
-    const int x = r - row0;
-    if (x < 0) return false;
-    const int m = x & ((1 << tshift) - 1);
-    return m < 8 && 8 * (x >> tshift) + m < rows;
-}
+// (band rows <-> image rows, the band's NDC edges and the reach test: backward_prep.h)
 // OWNER mode of a row band (dss_render_backward_owned): the occupancy surrogate of a point -- its whole window, over all image
 // rows, read from the FULL image gradient every rank holds -- is computed by the one rank whose band contains the image row
 // of the point's centre; the blend half stays with the rows that hold the fragments.  The position gradient of a (camera,
@@ -752,11 +610,6 @@ struct OwnArgs {
     const float *alpha;   // alpha channel of the full image gradient, (N, S, S) pixels `astride` floats apart; NULL: off
     int astride;
 };
-__device__ __forceinline__ int centre_image_row(float py, int S)
-{
-    const float fy = (1.0f - py) * 0.5f * (float)S;   // pixel row of the centre (any fixed partition of the axis does)
-    return min(max((int)fy, 0), S - 1);
-}
 
 // Owner mode, long lists: the dense alpha plane in FULL-image layout (N,S,S), filled only where an owned window can reach
 // -- the rows within the largest search radius (read from rs on the device: the medians run in front of this launch) of one
@@ -780,8 +633,8 @@ __global__ __launch_bounds__(256) void alpha_rows_kernel(const float *__restrict
 
 // Row band (multi-GPU), after the median: drop the visible points that cannot reach this rank's rows from the
 // segment lists, in place (one workgroup per segment: all entries are read into registers before any is
-// written), and zero their gradient rows (this band's partial sum for them is zero).  Same conservative test
-// as the gather kernel.  Without it every rank walks the whole visible list: 35 us of rejected tasks per step
+// written), and zero their gradient rows (this band's partial sum for them is zero).  The test is band_reached
+// (backward_prep.h).  Without it every rank walks the whole visible list: 35 us of rejected tasks per step
 // at 8 ranks even for a rank whose band is empty.
 template <int PER>
 __global__ __launch_bounds__(PREP_THREADS) void band_filter_kernel(
@@ -792,13 +645,10 @@ __global__ __launch_bounds__(PREP_THREADS) void band_filter_kernel(
 {
     __shared__ uint32_t s_w[PER * PREP_THREADS / 64];
     constexpr int SEG_PTS = PER * PREP_THREADS;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const unsigned seg = blockIdx.x;
     const uint32_t count = seg_count[seg];
-    // (tile-row-cyclic band: the last band row's image row bounds the band from below; the owned-row test follows)
-    const int last_row = row0 + (((rows - 1) >> 3) << tshift) + ((rows - 1) & 7);
-    const float band_lo = -1 + (2 * (S - 1 - last_row)) / (float)S;     // lower edge of the lowest pixel row
-    const float band_hi = -1 + (2 * (S - 1 - row0) + 2.0f) / (float)S;  // upper edge of the highest one
+    const BandEdges edges = band_edges(S, row0, rows, tshift);
     int32_t id[PER];
     uint32_t keep = 0;
 #pragma unroll
@@ -812,48 +662,18 @@ __global__ __launch_bounds__(PREP_THREADS) void band_filter_kernel(
             const int n = find_cloud(id[u], first_idx, num_pts, N);
             const float py = points[3 * (size_t)id[u] + 1], ry = radii[2 * (size_t)id[u] + 1];
             const float reach = own ? ry : fmaxf(n >= 0 ? rs[n] : 0.0f, ry);
-            bool in_band = n >= 0 && !(py + reach < band_lo || py - reach > band_hi);
-            if (in_band && tshift > 3) {
-                // cyclic band: some OWNED row must lie within reach (conservative pixel range, one pixel of slack each side)
-                int ylo, yhi;
-                in_band = ndc_index_range(py, reach, S, ylo, yhi) &&
-                          band_row_ceil(S - 1 - yhi, row0, tshift) <= min(band_row_floor(S - 1 - ylo, row0, tshift), rows - 1);
-            }
+            const bool in_band = n >= 0 && band_reached(py, reach, edges, tshift > 3, S, row0, rows, tshift);
             keep |= (in_band ? 1u : 0u) << u;
         }
     }
     uint32_t rank[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const unsigned long long m = __ballot((keep >> u) & 1u);
-        rank[u] = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (lane == 0) s_w[u * (PREP_THREADS / 64) + wid] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();  // every entry of the segment has been read
-    uint32_t tot = 0;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        uint32_t before = tot;
-#pragma unroll
-        for (int w = 0; w < PREP_THREADS / 64; ++w) {
-            const uint32_t c = s_w[u * (PREP_THREADS / 64) + w];
-            if (w < wid) before += c;
-            tot += c;
-        }
-        rank[u] += before;
-    }
+    const uint32_t tot = ordered_ranks<PER, PREP_THREADS>(keep, rank, s_w);   // (its barrier: every entry of the segment has been read)
     if (tid == 0) seg_count[seg] = tot;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
         if (id[u] < 0) continue;
-        if ((keep >> u) & 1u) {
-            vis_list[(size_t)seg * SEG_PTS + rank[u]] = id[u];
-        } else {
-            const size_t i = (size_t)id[u];
-            grad_pts[3 * i] = 0.0f; grad_pts[3 * i + 1] = 0.0f; grad_pts[3 * i + 2] = 0.0f;
-            if (grad_feat)
-                for (int ch = 0; ch < C; ++ch) grad_feat[i * C + ch] = 0.0f;
-        }
+        if ((keep >> u) & 1u) vis_list[(size_t)seg * SEG_PTS + rank[u]] = id[u];
+        else zero_grad_rows(grad_pts, grad_feat, C, (size_t)id[u]);
     }
 }
 
@@ -875,8 +695,8 @@ __global__ __launch_bounds__(PREP_THREADS) void band_filter_kernel(
 static inline size_t cell_blocks(int64_t P) { return (size_t)((P + CELL_CHUNK - 1) / CELL_CHUNK); }
 
 // Row band (multi-GPU, round 5): rs is known by now (median_final_kernel precedes this launch), so the entries that cannot
-// reach the rank's rows -- neither with their own box nor with the search window; the conservative test of
-// band_filter_kernel -- get no cell: they drop out of the sorted list the gather walks (at 8 ranks seven eighths of the
+// reach the rank's rows -- neither with their own box nor with the search window: band_reached, backward_prep.h -- get no
+// cell: they drop out of the sorted list the gather walks (at 8 ranks seven eighths of the
 // ~3.2M tasks of 8 x 1M points were rejected one by one inside the gather: 0.6 ms per rank and step for 0.16 ms of work) and
 // their zero partial sums are stored here.
 __global__ __launch_bounds__(CELL_SORT_THREADS) void cell_hist_kernel(
@@ -900,17 +720,9 @@ __global__ __launch_bounds__(CELL_SORT_THREADS) void cell_hist_kernel(
             const float px = points[3 * (size_t)p], py = points[3 * (size_t)p + 1];
             uint32_t key = screen_cell(px, py, n, S, cg);
             if (radii) {
-                const int last_row = row0 + (((rows - 1) >> 3) << tshift) + ((rows - 1) & 7);
-                const float band_lo = -1 + (2 * (S - 1 - last_row)) / (float)S;     // lower edge of the lowest pixel row
-                const float band_hi = -1 + (2 * (S - 1 - row0) + 2.0f) / (float)S;  // upper edge of the highest one
                 const float reach = own ? radii[2 * (size_t)p + 1] : fmaxf(rs[n], radii[2 * (size_t)p + 1]);
-                bool in_band = !(py + reach < band_lo || py - reach > band_hi);
-                if (in_band && tshift > 3) {
-                    int ylo, yhi;
-                    in_band = ndc_index_range(py, reach, S, ylo, yhi) &&
-                              band_row_ceil(S - 1 - yhi, row0, tshift) <= min(band_row_floor(S - 1 - ylo, row0, tshift), rows - 1);
-                }
-                if (!in_band) key = CELL_SORT_NONE;   // (its partial sums over this band are zero: visible_scan_kernel stored them)
+                // (a dropped point's partial sums over this band are zero: visible_scan_kernel stored them)
+                if (!band_reached(py, reach, band_edges(S, row0, rows, tshift), tshift > 3, S, row0, rows, tshift)) key = CELL_SORT_NONE;
             }
             cell_of[i] = key;
             if (key != CELL_SORT_NONE) atomicAdd(&s_hist[key], 1u);
@@ -1088,25 +900,6 @@ __device__ __forceinline__ unsigned long long fb_launch_tag()
     return dss_dispatch_id() * 0x9E3779B97F4A7C15ull ^ (q << 17) ^ (q >> 7) ^ 0x5851F42D4C957F2Dull;
 }
 
-// exclusive scan over the FB_THREADS threads of a workgroup (4 wavefronts); total left in every thread
-__device__ __forceinline__ uint32_t fb_block_excl_scan(uint32_t v, uint32_t *s_w /*[4]*/, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint32_t x = wave_incl_scan(v);
-    __syncthreads();
-    if (lane == 63) s_w[wid] = x;
-    __syncthreads();
-    uint32_t woff = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < FB_THREADS / 64; ++w) {
-        const uint32_t c = s_w[w];
-        if (w < wid) woff += c;
-        total += c;
-    }
-    return woff + x - v;
-}
-
 // Segment `c`: compaction + per-cloud bucket-sorted keys / bucket prefix.  s_mem: >= 2 * FB_BUCKETS + 160 words.
 // PER (= F.per) is a template parameter so that the loops over a thread's points unroll: all of their loads in flight
 // (as a runtime loop every load waited for the previous one: 5.5 us per segment instead of 3.5).
@@ -1155,16 +948,10 @@ __device__ __forceinline__ void fb_prep_segment(const FusedPrep &F, int c, const
     for (int u = 0; u < per; ++u) {
         const int64_t i = c0 + (int64_t)u * FB_THREADS + tid;
         const bool vis = (vmask >> u) & 1u;
-        const unsigned long long m = __ballot(vis);
-        if (vis) {
-            const uint32_t pos = s_pre[u * 4 + wid] +
-                                 __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            F.vis_list[c0 + pos] = (int32_t)i;
-        } else if (i < c1 && grad_pts) {
-            grad_pts[3 * i] = 0.0f; grad_pts[3 * i + 1] = 0.0f; grad_pts[3 * i + 2] = 0.0f;
-            if (grad_feat)
-                for (int ch = 0; ch < C; ++ch) grad_feat[(size_t)i * C + ch] = 0.0f;
-        }
+        uint32_t cnt_unused;
+        const uint32_t in_wave = lane_rank(vis, cnt_unused);
+        if (vis) F.vis_list[c0 + s_pre[u * 4 + wid] + in_wave] = (int32_t)i;
+        else if (i < c1 && grad_pts) zero_grad_rows(grad_pts, grad_feat, C, (size_t)i);
     }
     // per cloud that overlaps the segment (normally one): bucket counts, their prefix, then the keys in bucket order
     for (int n = 0; n < N; ++n) {
@@ -1177,14 +964,7 @@ __device__ __forceinline__ void fb_prep_segment(const FusedPrep &F, int c, const
     #pragma unroll
     for (int u = 0; u < per; ++u) {
             const int64_t i = c0 + (int64_t)u * FB_THREADS + tid;
-            const bool vis = (vmask >> u) & 1u;
-            const bool mine = vis && i >= lo && i < hi;
-            const unsigned long long mb = __ballot(vis && i < lo), mi = __ballot(mine);
-            if (lane == 0) {
-                if (mb) atomicAdd(&s_w[0], (uint32_t)__popcll(mb));
-                if (mi) atomicAdd(&s_w[1], (uint32_t)__popcll(mi));
-            }
-            if (mine) {
+            if (cloud_span_step((vmask >> u) & 1u, i, lo, hi, s_w)) {
                 const float2 r = KEEP ? rr[KEEP ? u : 0] : r2[i];
                 atomicAdd(&s_hist[fb_bucket(float_key(r.x))], 1u);
                 atomicAdd(&s_hist[fb_bucket(float_key(r.y))], 1u);
@@ -1194,7 +974,7 @@ __device__ __forceinline__ void fb_prep_segment(const FusedPrep &F, int c, const
         const uint32_t h = s_hist[tid];
         const uint32_t first_entry = s_w[0], entries = s_w[1];
         uint32_t total;
-        const uint32_t excl = fb_block_excl_scan(h, s_w + 4, total);
+        const uint32_t excl = block_excl_scan<FB_THREADS>(h, s_w + 4, total);
         F.chunk_hist[((size_t)n * F.chunks + c) * FB_BUCKETS + tid] = excl;
         s_cur[tid] = excl;
         if (tid == 0) F.seg_range[(size_t)n * F.chunks + c] = make_uint2(first_entry, entries);
@@ -1211,34 +991,6 @@ __device__ __forceinline__ void fb_prep_segment(const FusedPrep &F, int c, const
             }
         }
     }
-}
-
-// rank-k bin of a histogram held as h[NB] consecutive bins per thread (first bin of the thread: NB * tid)
-template <int NB>
-__device__ __forceinline__ void fb_select(const uint32_t (&h)[NB], uint32_t k, uint32_t *s_w /*[8]*/, uint32_t &bin_out,
-                                          uint32_t &k_out, uint32_t &cnt_out)
-{
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) v += h[i];
-    uint32_t total;
-    uint32_t excl = fb_block_excl_scan(v, s_w, total);
-    __syncthreads();
-    if (total > 0 && k >= excl && k < excl + v) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            if (k >= excl && k < excl + h[i]) {
-                s_w[4] = (uint32_t)(NB * threadIdx.x + i);
-                s_w[5] = k - excl;
-                s_w[7] = h[i];
-            }
-            excl += h[i];
-        }
-    }
-    __syncthreads();
-    bin_out = s_w[4];
-    k_out = s_w[5];
-    cnt_out = s_w[7];
 }
 
 // Median of cloud n (lower median of the radius keys of its visible points, rasterizer.py:885-888) from the segments'
@@ -1278,7 +1030,7 @@ __device__ __forceinline__ float fb_median(const FusedPrep &F, int n, const int6
         }
         reinterpret_cast<uint4 *>(s_cand + g * FB_BUCKETS)[qd] = acc;
         uint32_t all_keys;
-        (void)fb_block_excl_scan(2u * rg.y, s_w + 16, all_keys);   // two keys per visible point
+        (void)block_excl_scan<FB_THREADS>(2u * rg.y, s_w + 16, all_keys);   // two keys per visible point
         if (tid == 0) s_hist[FB_BUCKETS] = all_keys;               // all keys of the cloud
         s_cnt[tid] = 2u * rg.y;                                    // (keys of the segment, for the last bucket's end)
         s_base[tid] = 2u * (uint32_t)((int64_t)(c_lo + tid) * seg) + 2u * rg.x;   // first key of (cloud, segment) in F.keys
@@ -1288,7 +1040,7 @@ __device__ __forceinline__ float fb_median(const FusedPrep &F, int n, const int6
     __syncthreads();
     const uint32_t total0 = s_hist[FB_BUCKETS];
     if (total0 == 0) return 0.0f;   // uniform: nothing visible in this cloud
-    uint32_t k = (total0 - 1) / 2;  // torch.median = lower median
+    uint32_t k = lower_median_rank(total0);
     {
         const uint32_t lo_b = s_hist[tid], hi_b = s_hist[tid + 1];
         if (lo_b <= k && k < hi_b) { s_w[4] = (uint32_t)tid; s_w[5] = k - lo_b; s_w[6] = hi_b - lo_b; }
@@ -1307,7 +1059,7 @@ __device__ __forceinline__ float fb_median(const FusedPrep &F, int n, const int6
         }
         const uint32_t v = e1 - e0;
         uint32_t tot_unused;
-        const uint32_t ex = fb_block_excl_scan(v, s_w + 16, tot_unused);
+        const uint32_t ex = block_excl_scan<FB_THREADS>(v, s_w + 16, tot_unused);
         s_dst[tid] = ex;
         s_cnt[tid] = v;
         s_base[tid] += e0;
@@ -1375,8 +1127,9 @@ __device__ __forceinline__ float fb_median(const FusedPrep &F, int n, const int6
         __syncthreads();
         const uint4 hq = reinterpret_cast<const uint4 *>(s_hist)[tid];
         const uint32_t h[4] = {hq.x, hq.y, hq.z, hq.w};
-        uint32_t bin, left;
-        fb_select<4>(h, k, s_w, bin, k, left);
+        const RankBin sel = rank_select<FB_THREADS, 4, true>(h, 4u * (uint32_t)tid, k, false, s_w);   // (s_w[0..6])
+        const uint32_t bin = sel.bin, left = sel.count;
+        k = sel.k;
         const uint32_t nlo = lo + (bin << shift);
         const uint32_t span = (1u << shift) - 1u;
         hi = min(hi, nlo + span < nlo ? 0xffffffffu : nlo + span);
@@ -1541,7 +1294,7 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
     if (BAND) {
         // up to FB_MAX_SEG segments (one per thread): exclusive scan of their counts over the workgroup
         const uint32_t c = (int)threadIdx.x < n_seg ? vis_count[threadIdx.x] : 0u;
-        const uint32_t ex = fb_block_excl_scan(c, s_bscan, count);
+        const uint32_t ex = block_excl_scan<FB_THREADS>(c, s_bscan, count);
         s_bseg[threadIdx.x] = ex;
         if (threadIdx.x == 0) s_bseg[FB_MAX_SEG] = count;
     } else if (SEG) {
@@ -1682,43 +1435,35 @@ __global__ __launch_bounds__(256) void render_backward_kernel(
             }
         }
     }
-    // which = 0: by the splat's own box (blend half), 1: by the search radius (occupancy half; rs published).  Conservative
-    // (the task evaluates the exact rows); a rejected point's partial sum over this band is zero and is stored here.
+    // which = 0: by the splat's own box (blend half), 1: by the search radius (occupancy half; rs published): band_reached,
+    // backward_prep.h.  A rejected point's partial sum over this band is zero and is stored here.
     auto band_filter = [&](auto which_tag) {
         constexpr int WHICH = decltype(which_tag)::value;
-        const int last_row = row0 + (((rows - 1) >> 3) << tshift) + ((rows - 1) & 7);
-        const float band_lo = -1 + (2 * (S - 1 - last_row)) / (float)S;     // lower edge of the lowest pixel row
-        const float band_hi = -1 + (2 * (S - 1 - row0) + 2.0f) / (float)S;  // upper edge of the highest one
+        const BandEdges edges = band_edges(S, row0, rows, tshift);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             bool keep = false;
             if (b_id[j] >= 0 && b_n[j] >= 0) {
                 const float reach = WHICH == 0 ? b_ry[j] : s_brs[b_n[j]];
                 const float py = b_py[j];
-                keep = !(py + reach < band_lo || py - reach > band_hi);
-                if (WHICH == 1 && OW.alpha != nullptr) {
+                if (WHICH == 1 && OW.alpha != nullptr)
                     keep = band_owns_row(centre_image_row(py, S), row0, rows, tshift);   // owner mode: whole windows of the own centres
-                } else
-                if (keep && CYC) {
-                    int ylo, yhi;
-                    keep = ndc_index_range(py, reach, S, ylo, yhi) &&
-                           band_row_ceil(S - 1 - yhi, row0, tshift) <= min(band_row_floor(S - 1 - ylo, row0, tshift), rows - 1);
-                }
+                else
+                    keep = band_reached(py, reach, edges, CYC, S, row0, rows, tshift);
             }
-            const unsigned long long m = __ballot(keep);
+            uint32_t kept;
+            const uint32_t in_wave = lane_rank(keep, kept);
             uint32_t base = 0;
-            if (lane == 0 && m) base = atomicAdd(&s_bcnt[WHICH], (uint32_t)__popcll(m));
+            if (lane == 0 && kept) base = atomicAdd(&s_bcnt[WHICH], kept);
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
             if (keep) {
-                s_band[WHICH * BAND_SHARE + base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] =
-                    (int)threadIdx.x + 256 * j;   // the share slot: its record is in s_rec
+                s_band[WHICH * BAND_SHARE + base + in_wave] = (int)threadIdx.x + 256 * j;   // the share slot: its record is in s_rec
             } else if (b_id[j] >= 0) {
-                const size_t i = (size_t)b_id[j];
+                // (each half zeroes the row it would have written)
                 if (WHICH == 0) {
-                    if (grad_feat)
-                        for (int ch = 0; ch < Cn; ++ch) grad_feat[i * Cn + ch] = 0.0f;
+                    if (grad_feat) zero_feat_row(grad_feat, Cn, (size_t)b_id[j]);
                 } else {
-                    grad_pts[3 * i] = 0.0f; grad_pts[3 * i + 1] = 0.0f; grad_pts[3 * i + 2] = 0.0f;
+                    zero_pts_row(grad_pts, (size_t)b_id[j]);
                 }
             }
         }

@@ -426,12 +426,15 @@ ORACLE_CASES = tuple(n for n in CASES if n != "long")       # (the oracle's wind
 
 def band_rows(name):
     """the row sets of the band cases: the contiguous bands (0, 40, S), twelve bands of 8 rows (the last one shorter or
-    longer at S = 100), and the tile-row-cyclic partition of 4 -> [(label, `rows` argument of the entry, image rows)]"""
+    longer at S = 100), and the tile-row-cyclic partition of 4 -> [(label, `rows` argument of the entry, image rows)].
+    `long` (S = 256): the two contiguous bands (0, 104, S) and the cyclic partition of 4 only"""
     from dss_amd.distributed import RowPartition
     S = case(name).S
-    out = [("rows %d-%d" % (a, b), (a, b), list(range(a, b))) for a, b in ((0, 40), (40, S))]
-    cuts = list(range(0, 88 + 1, 8)) + [S]
-    out += [("rows %d-%d" % (a, b), (a, b), list(range(a, b))) for a, b in zip(cuts[:-1], cuts[1:])]
+    cut = 104 if name == "long" else 40
+    out = [("rows %d-%d" % (a, b), (a, b), list(range(a, b))) for a, b in ((0, cut), (cut, S))]
+    if name != "long":
+        cuts = list(range(0, 88 + 1, 8)) + [S]
+        out += [("rows %d-%d" % (a, b), (a, b), list(range(a, b))) for a, b in zip(cuts[:-1], cuts[1:])]
     for g in range(4):
         part = RowPartition(S, 4, g, cyclic=True)
         out.append(("cyclic %d of 4" % g, part.rows, list(part.row_indices())))

@@ -120,6 +120,33 @@ def test_band_references_add_up_to_the_whole_image():
             assert np.array_equal(sum(p.pairs for p in parts), whole.pairs)
 
 
+def test_long_bands_add_up_and_every_band_drops_and_keeps_visible_points():
+    """`long` in two contiguous bands (0, 104, 256) and the tile-row-cyclic partition of 4: the band references add up to the
+    whole image, and the band filter of the long-list path has something to do on every band -- visible points that no filter
+    may drop (the centre of an owned row lies within max(rs, ry) of them) and visible points that every conservative filter
+    of the kind drops (no owned row within max(rs, ry) + 3 pixels: the filter's slack is a pixel or two)."""
+    c, whole = gr.case("long"), gr.reference("long")
+    bands = gr.band_rows("long")
+    assert c.P > 262144 and int(c.vis.sum()) < 5000 and len(bands) == 6
+    vis = c.vis.astype(bool)
+    cloud = np.searchsorted(c.first, np.arange(c.P), side="right") - 1
+    reach = np.maximum(whole.rs[cloud], c.radii[:, 1])[vis].astype(np.float64)
+    py = c.pts[vis, 1].astype(np.float64)
+    for group in (bands[:2], bands[2:]):
+        assert sorted(r for _l, _a, rows in group for r in rows) == list(range(c.S))
+        parts = [gr.reference("long", tuple(rows)) for _l, _a, rows in group]
+        for out, scale in (("pts", whole.pts_A), ("pts_A", whole.pts_A), ("feat", whole.feat_A), ("feat_A", whole.feat_A)):
+            total = sum(getattr(p, out) for p in parts)
+            assert (np.abs(total - getattr(whole, out)) <= 1e-13 * scale).all(), out
+        assert np.array_equal(sum(p.pairs for p in parts), whole.pairs)
+        for label, _arg, rows in group:
+            centres = gr.pix_to_ndc(c.S - 1 - np.asarray(rows), c.S).astype(np.float64)
+            nearest = np.abs(py[:, None] - centres[None]).min(1)
+            must_keep, must_drop = int((nearest <= reach).sum()), int((nearest > reach + 6.0 / c.S).sum())
+            print("long %-16s of %d visible points: %d must be kept, %d are dropped by any such filter" % (label, py.size, must_keep, must_drop))
+            assert must_keep > 0 and must_drop > 0, label
+
+
 @pytest.mark.parametrize("mut,name", [(m, n) for m, (_out, names) in gr.MUTATIONS.items() for n in names])
 def test_wrong_formulas_lie_ten_times_beyond_the_bar(mut, name):
     out = gr.MUTATIONS[mut][0]

@@ -102,6 +102,17 @@ the forward's weight sums, with wsum = None and, on the default path, without fe
     band100        owner mode contiguous plane  2.8e-07/2e-06/1.2e-07    -                        -
     band100        owner mode cyclic image      2.8e-07/2e-06/1.2e-07    -                        -
     band100        owner mode cyclic plane      2.8e-07/2e-06/1.2e-07    -                        -
+    the other two band filters (`band_filter_kernel` with DSS_OPT_BACKWARD_FUSED = 1; `cell_hist_kernel` on `long`, bands
+    (0, 104, 256) and cyclic of 4, the case's whole-image bars), largest figure over the bands:
+    band96         fused1, 2 + 12 contiguous    2.6e-07/2e-06/1.5e-07    2.5e-07/2e-06/2.1e-07    -
+    band96         fused1, 4 tile-row-cyclic    2.6e-07/2e-06/1.5e-07    2.5e-07/2e-06/2.1e-07    -
+    band100        fused1, 2 + 12 contiguous    2.8e-07/2e-06/1.5e-07    2.4e-07/1e-06/2.0e-07    -
+    band100        fused1, 4 tile-row-cyclic    2.8e-07/2e-06/1.5e-07    2.4e-07/1e-06/2.0e-07    -
+    band96/100     fused1, owner mode (all 8)   2.8e-07/2e-06/1.2e-07    -                        -
+    long           band, 2 contiguous           2.9e-07/2e-06/1.5e-07    2.0e-07/9e-07/1.6e-07    -
+    long           band, 4 tile-row-cyclic      2.9e-07/2e-06/2.1e-07    2.0e-07/9e-07/1.8e-07    -
+    long           owner mode (all 4)           2.9e-07/2e-06/1.5e-07    -                        -
+    (`ops.backward_radius` on `long`, the only user of `median_hist_kernel<0>`: the reference's bits.)
 
     the unfused entries (test_unfused_entries_against_fp64): fp32 / bar / kernel
     case           splat_backward           + grad_zbuf: xy          + grad_zbuf: z           + grad_zbuf + clip 0.05
@@ -263,13 +274,38 @@ def test_unfused_entries_against_fp64(name):
     hold("blend gather+wsum", blend(geometry=geom, wsum=d["wsum"]), ref.feat, ref.feat_A, "feat")
 
 
+def _row_bands(name, tag, **options):
+    """every band of `gr.band_rows`: the band's partial gradients against the reference restricted to the band's rows"""
+    c = gr.case(name)
+    for label, rows_arg, rows in gr.band_rows(name):
+        with _options(c.N, **options):
+            gf, gp = _render(name, band=(rows_arg, rows))
+        _check("%s %s%s" % (name, label, tag), name, gf, gp, gr.reference(name, tuple(rows)))
+
+
+def _owner_mode(name, layout, plane, tag, **options):
+    """owner mode of the two contiguous bands, or of the cyclic partition of 4 (the last four entries of `gr.band_rows`)"""
+    c, d, whole = gr.case(name), _dev(name), gr.reference(name)
+    bands = gr.band_rows(name)
+    owners, total = torch.zeros(c.P, device=DEV), torch.zeros((c.P, 3), device=DEV)
+    for label, rows_arg, rows in (bands[:2] if layout == "contiguous" else bands[-4:]):
+        kw = dict(grad_occ_full=d["go"][..., c.C].contiguous()) if plane else dict(grad_out_full=d["go"])
+        with _options(c.N, **options):
+            gf, gp = _render(name, band=(rows_arg, rows), **kw)
+        part = gr.reference(name, tuple(rows))
+        _ratio("%s owner %s%s" % (name, label, tag), "grad_features", gf, part.feat, part.feat_A, gr.BARS[name]["feat"])
+        owners += (gp != 0).any(dim=1).float()
+        total += gp            # (zeros on every rank but the owner: the sum IS the owner's entry)
+    has_term = torch.from_numpy((whole.pts_A > 0).any(1)).to(DEV)
+    assert float(owners.max()) <= 1.0 and bool((owners[has_term] == 1).all())
+    _check("%s owner mode %s %s%s" % (name, layout, "plane" if plane else "image", tag), name, None, total, whole)
+
+
 @pytest.mark.parametrize("name", ["band96", "band100"])
 def test_row_bands_against_fp64(name):
     """contiguous bands (0, 40, S), twelve bands of 8 rows and a tile-row-cyclic partition of 4: every band's partial
     gradients against the reference restricted to the band's rows, with the scale of those rows"""
-    for label, rows_arg, rows in gr.band_rows(name):
-        gf, gp = _render(name, band=(rows_arg, rows))
-        _check("%s %s" % (name, label), name, gf, gp, gr.reference(name, tuple(rows)))
+    _row_bands(name, "")
 
 
 @pytest.mark.parametrize("plane", [False, True], ids=["grad_out_full", "grad_occ_full"])
@@ -279,16 +315,40 @@ def test_owner_mode_against_fp64(name, layout, plane):
     """owner mode of a band: every point has a non-zero position gradient on at most one rank, every point with A > 0 on
     exactly one, and that rank's entry is the WHOLE-image reference's at the whole-image bar; the feature gradients are the
     band's partial sums"""
-    c, d, whole = gr.case(name), _dev(name), gr.reference(name)
-    bands = gr.band_rows(name)
-    owners, total = torch.zeros(c.P, device=DEV), torch.zeros((c.P, 3), device=DEV)
-    for label, rows_arg, rows in (bands[:2] if layout == "contiguous" else bands[14:]):
-        kw = dict(grad_occ_full=d["go"][..., c.C].contiguous()) if plane else dict(grad_out_full=d["go"])
-        gf, gp = _render(name, band=(rows_arg, rows), **kw)
-        part = gr.reference(name, tuple(rows))
-        _ratio("%s owner %s" % (name, label), "grad_features", gf, part.feat, part.feat_A, gr.BARS[name]["feat"])
-        owners += (gp != 0).any(dim=1).float()
-        total += gp            # (zeros on every rank but the owner: the sum IS the owner's entry)
-    has_term = torch.from_numpy((whole.pts_A > 0).any(1)).to(DEV)
-    assert float(owners.max()) <= 1.0 and bool((owners[has_term] == 1).all())
-    _check("%s owner mode %s %s" % (name, layout, "plane" if plane else "image"), name, None, total, whole)
+    _owner_mode(name, layout, plane, "")
+
+
+@pytest.mark.parametrize("name", ["band96", "band100"])
+def test_row_bands_on_the_round3_filter_against_fp64(name):
+    """the same bands, references and bars with DSS_OPT_BACKWARD_FUSED = 1: the list is filtered by `band_filter_kernel`
+    behind `median_visible_kernel`, not inside the gather launch"""
+    _row_bands(name, " fused1", fused=1)
+
+
+@pytest.mark.parametrize("plane", [False, True], ids=["grad_out_full", "grad_occ_full"])
+@pytest.mark.parametrize("layout", ["contiguous", "cyclic"])
+@pytest.mark.parametrize("name", ["band96", "band100"])
+def test_owner_mode_on_the_round3_filter_against_fp64(name, layout, plane):
+    """owner mode with DSS_OPT_BACKWARD_FUSED = 1: `band_filter_kernel` keeps by the own box, the gather tests the owner"""
+    _owner_mode(name, layout, plane, " fused1", fused=1)
+
+
+def test_row_bands_on_the_long_list_filter_against_fp64():
+    """`long` (P > 262,144, fewer than 5,000 visible points) in two contiguous bands and in a tile-row-cyclic partition of 4:
+    the filter sits in `cell_hist_kernel`; the whole-image bars of the case.  (`tests/test_gather_reference_cpu.py`: every band
+    drops visible points and keeps others, and the band references add up to the whole image.)"""
+    _row_bands("long", "")
+
+
+@pytest.mark.parametrize("plane", [False, True], ids=["grad_out_full", "grad_occ_full"])
+@pytest.mark.parametrize("layout", ["contiguous", "cyclic"])
+def test_owner_mode_on_the_long_list_filter_against_fp64(layout, plane):
+    _owner_mode("long", layout, plane, "")
+
+
+def test_long_list_radius_has_the_reference_bits():
+    """`ops.backward_radius` above 262,144 points: the only user of `median_hist_kernel<0>`"""
+    c, d = gr.case("long"), _dev("long")
+    assert c.P > 262144
+    rs = ops.backward_radius(d["radii"], d["vis"], d["first"], d["num"], c.radii_s)
+    assert np.array_equal(rs.cpu().numpy(), gr.reference("long").rs)
