@@ -19,8 +19,9 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(
     if (i >= npix) return;
     const int Cn = (C > 0) ? C : Crt;
     constexpr int CM = (C > 0) ? C : BLEND_MAX_C;
-    // Summation order = the fused epilogue's (fine_tile, raster_forward.hip): lane j of a pixel's quad sums the fragments
-    // k = j, j + 4, ... in ascending k, the four partial sums are combined as (p0 + p1) + (p2 + p3) -- bit-identical results.
+    // Summation order = the fused epilogues' (epilogue_packed and fine_tile, raster_forward.hip): lane j of a pixel's quad sums the fragments
+    // k = j, j + 4, ... in ascending k, the four partial sums are combined as (p0 + p1) + (p2 + p3), the order of quad_sum
+    // (common.h) -- bit-identical results.
     float pc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int k0 = 0; k0 < K; k0 += 4) {
 #pragma unroll

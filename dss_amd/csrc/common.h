@@ -51,6 +51,16 @@ __device__ __forceinline__ bool ndc_index_range_tight(float x, float r, int S, i
     return lo <= hi;
 }
 
+// Sum over a lane quad (lanes 4i .. 4i+3), left in all four lanes: (v0 + v1) + (v2 + v3) as seen from lane 0 -- first the
+// lanes 1 apart, then the lanes 2 apart.  This is the order in which blend_forward_kernel (blend.hip) and the fine pass's
+// fused blend add a pixel's four partial sums: the two are bit-identical only while both keep it.
+__device__ __forceinline__ float quad_sum(float v)
+{
+    v += dpp_f32<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp_f32<0x4E>(v);   // quad_perm [2,3,0,1]
+    return v;
+}
+
 __device__ __forceinline__ float wave_sum(float v)
 {
     v += dpp_f32<0xB1>(v);   // quad_perm [1,0,3,2]

@@ -952,6 +952,17 @@ struct FineArgs {
 // one unsigned 64-bit compare implements the strict total order (z, idx) of
 // rasterize_points_cpu.cpp:85 / oracle frag_less.  Empty slots hold ~0.
 #define KEY_EMPTY 0xffffffffffffffffull
+// The key packing, stated once.  The depth a caller packs is pz + 0.0f: -0 becomes +0 (pz = -0 passes the reference's `pz < 0`
+// cull), whose bit pattern orders like the value; the bits of -0 would sort behind every positive depth.  The fine pass stages
+// (id bits, pz + 0.0f) as one float2 and reads the pair back as this 64-bit word.
+__device__ __forceinline__ unsigned long long frag_key(float z, unsigned id) { return ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)id; }
+__device__ __forceinline__ unsigned key_depth_bits(unsigned long long key) { return (unsigned)(key >> 32); }
+__device__ __forceinline__ float key_depth(unsigned long long key) { return __uint_as_float(key_depth_bits(key)); }
+__device__ __forceinline__ int key_id(unsigned long long key) { return (int)(unsigned)(key & 0xffffffffull); }
+
+// The conic form Q of a splat at the offset (dx, dy) from its centre: rasterize_points.cu:92-101, same expression order
+// (and no FMA contraction: -ffp-contract=off), so that Q has the reference's bits wherever it is formed.
+__device__ __forceinline__ float ewa_q(float a, float b, float c, float dx, float dy) { return a * dx * dx + b * dx * dy + c * dy * dy; }
 
 // sorted insertion of ekey into an ascending K-list held in registers; branch-free.  The list holds the 64-bit keys only:
 // the Q value of a fragment is recomputed from its record in the epilogue, for the K survivors of a pixel instead of being
@@ -1169,6 +1180,188 @@ __device__ __forceinline__ const FineArgs &reloaded_args()
     return *(const FineArgs *)(const char *)kp;
 }
 
+// Latency-bound launches (every occupied tile resident at once, the launch lasts as long as its slowest tile:
+// 20 us against a 10 us mean at 512^2): waves of heavy tiles get issue priority over the light tiles and the fill
+// workgroups they share a SIMD with (fine pass 23.9 -> 21.7 us; thresholds 100..280 all measure the same).
+// Throughput-bound launches lose 2 % with it, so the host only sets the flag for <= 4096 tiles.
+__device__ __forceinline__ void set_tile_priority(const FineArgs &A, const uint32_t (&cs)[DSS_SUB])
+{
+    if (A.prio) {
+        uint32_t tot = 0;
+#pragma unroll
+        for (int q = 0; q < DSS_SUB; ++q) tot += cs[q];
+        if (tot > 220u) __builtin_amdgcn_s_setprio(3);
+        else if (tot > 140u) __builtin_amdgcn_s_setprio(2);
+        else __builtin_amdgcn_s_setprio(1);
+    }
+}
+
+// Candidate p of the chunk -> slot dst of the three LDS record arrays, from whichever record layout the call has: cell-ordered
+// crec, 64-byte rec, or the four separate arrays.  Runs between the chunk loop's two barriers.  Depths are staged as pz + 0.0f
+// (see frag_key).
+template <bool PACKED>
+__device__ __forceinline__ void stage_candidate(const FineArgs &A, const bool use_list, const bool have, int64_t p, const int dst,
+                                                float4 *s_geo, float4 *s_ell, float2 *s_zid)
+{
+    // (cell-ordered path without packed records -- more than 8 fragments per pixel, other channel counts --: the entry is a
+    // position, the per-point arrays are indexed by the splat id)
+    if (!PACKED && have && use_list && A.crec != nullptr) p = A.sort_id[p];
+    if (have) {
+        if (PACKED && use_list && A.crec != nullptr) {
+            // cell-ordered path: the list entry is a POSITION of the point order; its 32-byte candidate record and its id
+            // sit next to those of the tile's other candidates (4 records per 128-byte line, shared with the
+            // neighbouring tiles on the same XCD)
+            const float4 *C = A.crec + 2 * p;
+            const float4 c1 = C[1];
+            s_geo[dst] = C[0];
+            s_ell[dst] = make_float4(c1.x, c1.y, c1.z, A.cutoffC);
+            s_zid[dst] = make_float2(__int_as_float(A.sort_id[p]), c1.w + 0.0f);
+        } else if (PACKED) {
+            // one 64-byte record = one half cache line per candidate: three loads, one memory transaction (the four
+            // separate arrays cost four transactions, and every XCD ended up fetching every line of all of them:
+            // point ids are spatially random, so each 128-byte line held a point of every screen region)
+            const float4 *R = A.rec + 4 * p;
+            s_geo[dst] = R[0];
+            s_ell[dst] = R[1];
+            s_zid[dst] = make_float2(__int_as_float((int)p), R[3].x + 0.0f);
+        } else {
+            const float px = A.points[3 * p], py = A.points[3 * p + 1], pz = A.points[3 * p + 2];
+            const float2 rr = reinterpret_cast<const float2 *>(A.radii)[p];
+            s_geo[dst] = make_float4(px, py, rr.x, rr.y);
+            s_ell[dst] = make_float4(A.ellipse[3 * p], A.ellipse[3 * p + 1], A.ellipse[3 * p + 2], A.cutoff[p]);
+            s_zid[dst] = make_float2(__int_as_float((int)p), pz + 0.0f);
+        }
+    }
+}
+
+// Cull + compact of a staged chunk of m candidates, by one wavefront: one candidate per lane, ballot, prefix popcount -> the
+// wavefront's per-slice survivor lists `surv`, padded with the sentinel slot to whole two-survivor passes.  Returns the number
+// of survivors.  The footprint's NDC bounds and the depth cut are wave-uniform.
+__device__ __forceinline__ int cull_compact(const FineArgs &A, const int lane, const float f_xmin, const float f_xmax, const float f_ymin,
+                                            const float f_ymax, const int m, const unsigned cut_k, const unsigned cut_0,
+                                            const float4 *s_geo, const float2 *s_zid, unsigned short *surv)
+{
+    int nsurv = 0;
+    for (int sub64 = 0; sub64 < m; sub64 += 64) {
+        const int j = sub64 + lane;
+        bool keep = false;
+        if (j < m) {
+            const float4 ge = s_geo[j];
+            // conservative, rounding-monotone rejection against the footprint (see splat_tile_rect); bitwise on
+            // purpose: short-circuit forms compile to nested exec-mask branches
+            const float ez = s_zid[j].y;
+            const bool out = (int)(ez < 0) | (int)((f_xmax - ge.x) < -ge.z) | (int)((f_xmin - ge.x) > ge.z) |
+                             (int)((f_ymax - ge.y) < -ge.w) | (int)((f_ymin - ge.y) > ge.w) |
+                             (int)(__float_as_uint(ez) > cut_k) | (int)(ez - __uint_as_float(cut_0) > A.thr);
+            keep = !out;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            const int rank = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
+                                                               __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            // survivor `rank` -> slice rank%4; stored as the byte offset of its 16-byte records
+            surv[(rank & 3) * (CHUNK / 4) + (rank >> 2)] = (unsigned short)(j * 16);
+        }
+        nsurv += __popcll(mask);
+    }
+    {   // pad to a whole number of two-survivor passes of all four slices with the sentinel slot
+        const int rank = nsurv + lane;
+        if (lane < 8 && rank < ((nsurv + 7) & ~7)) surv[(rank & 3) * (CHUNK / 4) + (rank >> 2)] = (unsigned short)(CHUNK * 16);
+    }
+    // same wavefront wrote and now reads `surv`: LDS ops of one wave complete in order; the wave
+    // barrier only stops the compiler from moving the reads above the writes
+    __builtin_amdgcn_wave_barrier();
+    return nsurv;
+}
+
+// Epilogue with packed records (K <= 8, RGB, fused blend), by all four lanes of a pixel's quad: Q of the lane's fragments mi[]
+// into mq[], visibility flags, and -- by the lane with in_img -- occupancy, weight sum and RGBA of pixel `pix` at NDC (xf_e, yf_e),
+// band row lr_e, column c_e of camera n.  Every index comes from fine_tile's second laundered thread id.
+// Ep is the RE-READ argument block, handed over as a POINTER: a `const FineArgs &` parameter is dereferenceable by contract, which
+// lets the compiler hoist the loads of the output pointers -- what reloaded_args() is there to prevent.
+template <int MQ>
+__device__ __forceinline__ void epilogue_packed(const FineArgs *Ep, const float xf_e, const float yf_e, const bool in_img, const size_t pix, const int n,
+                                                const int lr_e, const int c_e, const bool any, const int (&mi)[MQ], float (&mq)[MQ])
+{
+    const FineArgs &E = *Ep;
+    float wk[MQ];
+    float cum = 0.0f;
+    // records of the lane's fragments: {px,py,..} {a,b,c,..} for Q and {scaler,f0,f1,f2} for the blend, one round trip
+    float2 gp[MQ];
+    float4 ge[MQ], br[MQ];
+#pragma unroll
+    for (int m = 0; m < MQ; ++m) {
+        gp[m] = make_float2(0.f, 0.f);
+        ge[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+        br[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (mi[m] >= 0) {
+            const float4 *R = E.rec + 4 * (size_t)mi[m];
+            gp[m] = *reinterpret_cast<const float2 *>(R);
+            ge[m] = R[1];
+            br[m] = R[2];
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MQ; ++m) {
+        wk[m] = 0.0f;
+        if (mi[m] >= 0) {
+            const float dx = xf_e - gp[m].x;
+            const float dy = yf_e - gp[m].y;
+            mq[m] = ewa_q(ge[m].x, ge[m].y, ge[m].z, dx, dy);
+            if (E.visible) E.visible[mi[m]] = 1;
+            wk[m] = ewa_weight(mq[m], br[m].x);
+            cum += wk[m];
+        }
+    }
+    // fused blend (same arithmetic and order as blend_forward_kernel): w = exp(-q/2) * scaler, img = sum f * (w / cum)
+    cum = quad_sum(cum);
+    if (cum < 1e-4f) cum = 1e-4f;
+    const float inv_cum = fast_rcp(cum);
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int m = 0; m < MQ; ++m) {
+        if (mi[m] >= 0) {
+            const float wn = wk[m] * inv_cum;
+            a0 += br[m].y * wn;
+            a1 += br[m].z * wn;
+            a2 += br[m].w * wn;
+        }
+    }
+    a0 = quad_sum(a0);
+    a1 = quad_sum(a1);
+    a2 = quad_sum(a2);
+    if (in_img) {
+        E.occ[pix] = any ? 1.0f : 0.0f;
+        E.wsum[pix] = cum;
+        float *o = E.image + (size_t)n * E.img_sn + (size_t)lr_e * E.img_sr + (size_t)c_e * 4;
+        // RGBA as ONE 16-byte store per pixel (four dword stores at a 16-byte stride quadruple the write requests)
+        *reinterpret_cast<float4 *>(o) = make_float4(a0, a1, a2, any ? 1.0f : 0.0f);
+    }
+}
+
+// The fine pass of one tile.  Its stages in order; a NAME( is a function above, the others are written out here because as a
+// function each changes the instruction count of the instantiations named (same flags, against the written-out form;
+// profiles/fine_stages_refactor.txt has every figure):
+//   tile and lane facts       n, tx, ty, lane roles (wid through readfirstlane), pixel centre, footprint bounds
+//                             [as a struct with a constructor: every instantiation, +6 VGPRs with the source below]
+//   candidate source          counters -> cs[] (indexed by unrolled constants ONLY), use_list, c_mine, cmax, lbase / pbase, first
+//                             speculative list entry; with the wait on the in-launch pool pass
+//                             [open_source: all 20, +1 .. +73, +6 VGPRs at K <= 16; pool_ready alone: all 20, -15 .. +32]
+//   set_tile_priority(        s_setprio from the tile's total
+//   extent                    first / count / step
+//   per chunk:  chunk slot    have, p, dst, m; requests the next chunk's list entry  [chunk_slot: all 20, -32 .. +297 at K = 32]
+//               BARRIER, stage_candidate<PACKED>( , BARRIER
+//               cull_compact( -> nsurv
+//               test + insert two survivors a pass; the empty asm pins the seven LDS reads
+//                             [test_insert: 18 of 20, +1 .. +24, K = 7 without records -29: the LDS loads take another alignment]
+//               depth cut     when another chunk follows  [refresh_depth_cut: 16 of 20 get SMALLER, -1 .. -17, up to -10 VGPRs]
+//   reloaded_args()           the kernel arguments re-read: first thing after the loop, the only source of E
+//   workspace reset           from a laundered thread id  [reset_tile_state: fine_kernel<24, false> +8]
+//   merge_round( x 2
+//   the SECOND laundered thread id -> quad indices, depth merge, the lane's fragments
+//                             [depth_merge_bits: 7 of 20, -29 .. +22; pick_fragments: 11 of 20, -3 .. +49]
+//   epilogue_packed<MQ>(      or the per-point-array epilogue  [epilogue_arrays: K = 1, 3, 16, 24, 32 without records, -1 .. +5]
+//   LDS transpose             three planes at once, or one after the other  [store_planes: K = 12 .. 32, +18 .. +73]
 template <int KMAX, bool PACKED>
 __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int tile_id, int32_t *slot_to_clear)
 {
@@ -1177,7 +1370,7 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
     // slot CHUNK of each array is a sentinel that no pixel hits (negative radii): it pads the survivor lists to whole passes
     __shared__ float4 s_geo[CHUNK + 1];   // px, py, rx, ry
     __shared__ float4 s_ell[CHUNK + 1];   // a, b, c, cutoff
-    __shared__ float2 s_zid[CHUNK + 1];   // idx (bits), pz + 0.0f: read as ONE 64-bit word this is the fragment's sort key
+    __shared__ float2 s_zid[CHUNK + 1];   // idx (bits), pz + 0.0f: read as ONE 64-bit word this is the fragment's sort key (frag_key)
     __shared__ unsigned short s_surv[FINE_WAVES][4][CHUNK / 4];  // per wavefront and slice: compacted survivor slots
     constexpr int PLANES = (KMAX <= 8) ? 3 : 1;   // idx / zbuf / qvalue staged together when they fit
     __shared__ int s_out[PLANES][DSS_TILE_PIX * KMAX];
@@ -1281,18 +1474,7 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
 #pragma unroll
         for (int q = 0; q < DSS_SUB; ++q) cs[q] = 0;
     }
-    if (A.prio) {
-        // Latency-bound launches (every occupied tile resident at once, the launch lasts as long as its slowest tile:
-        // 20 us against a 10 us mean at 512^2): waves of heavy tiles get issue priority over the light tiles and the fill
-        // workgroups they share a SIMD with (fine pass 23.9 -> 21.7 us; thresholds 100..280 all measure the same).
-        // Throughput-bound launches lose 2 % with it, so the host only sets the flag for <= 4096 tiles.
-        uint32_t tot = 0;
-#pragma unroll
-        for (int q = 0; q < DSS_SUB; ++q) tot += cs[q];
-        if (tot > 220u) __builtin_amdgcn_s_setprio(3);
-        else if (tot > 140u) __builtin_amdgcn_s_setprio(2);
-        else __builtin_amdgcn_s_setprio(1);
-    }
+    set_tile_priority(A, cs);
     int64_t first = 0, count = cmax;
     if (!use_list) {
         first = A.first_idx[n];
@@ -1374,68 +1556,10 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
             m = (int)min((int64_t)CHUNK, count - base);
         }
         __syncthreads();  // previous chunk fully consumed
-        // (cell-ordered path without packed records -- more than 8 fragments per pixel, other channel counts --: the entry is a
-        // position, the per-point arrays are indexed by the splat id)
-        if (!PACKED && have && use_list && A.crec != nullptr) p = A.sort_id[p];
-        if (have) {
-            if (PACKED && use_list && A.crec != nullptr) {
-                // cell-ordered path: the list entry is a POSITION of the point order; its 32-byte candidate record and its id
-                // sit next to those of the tile's other candidates (4 records per 128-byte line, shared with the
-                // neighbouring tiles on the same XCD)
-                const float4 *C = A.crec + 2 * p;
-                const float4 c1 = C[1];
-                s_geo[dst] = C[0];
-                s_ell[dst] = make_float4(c1.x, c1.y, c1.z, A.cutoffC);
-                s_zid[dst] = make_float2(__int_as_float(A.sort_id[p]), c1.w + 0.0f);
-            } else if (PACKED) {
-                // one 64-byte record = one half cache line per candidate: three loads, one memory transaction (the four
-                // separate arrays cost four transactions, and every XCD ended up fetching every line of all of them:
-                // point ids are spatially random, so each 128-byte line held a point of every screen region)
-                const float4 *R = A.rec + 4 * p;
-                s_geo[dst] = R[0];
-                s_ell[dst] = R[1];
-                s_zid[dst] = make_float2(__int_as_float((int)p), R[3].x + 0.0f);
-            } else {
-                const float px = A.points[3 * p], py = A.points[3 * p + 1], pz = A.points[3 * p + 2];
-                const float2 rr = reinterpret_cast<const float2 *>(A.radii)[p];
-                s_geo[dst] = make_float4(px, py, rr.x, rr.y);
-                s_ell[dst] = make_float4(A.ellipse[3 * p], A.ellipse[3 * p + 1], A.ellipse[3 * p + 2], A.cutoff[p]);
-                s_zid[dst] = make_float2(__int_as_float((int)p), pz + 0.0f);
-            }
-        }
+        stage_candidate<PACKED>(A, use_list, have, p, dst, s_geo, s_ell, s_zid);
         __syncthreads();
         if (base == 0) FT_MARK(2);
-        // ---- cull + compact: one candidate per lane, ballot, prefix popcount -> per-slice survivor lists ----
-        int nsurv = 0;
-        for (int sub64 = 0; sub64 < m; sub64 += 64) {
-            const int j = sub64 + lane;
-            bool keep = false;
-            if (j < m) {
-                const float4 ge = s_geo[j];
-                // conservative, rounding-monotone rejection against the footprint (see splat_tile_rect); bitwise on
-                // purpose: short-circuit forms compile to nested exec-mask branches
-                const float ez = s_zid[j].y;
-                const bool out = (int)(ez < 0) | (int)((f_xmax - ge.x) < -ge.z) | (int)((f_xmin - ge.x) > ge.z) |
-                                 (int)((f_ymax - ge.y) < -ge.w) | (int)((f_ymin - ge.y) > ge.w) |
-                                 (int)(__float_as_uint(ez) > cut_k) | (int)(ez - __uint_as_float(cut_0) > A.thr);
-                keep = !out;
-            }
-            const unsigned long long mask = __ballot(keep);
-            if (keep) {
-                const int rank = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
-                                                                   __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                // survivor `rank` -> slice rank%4; stored as the byte offset of its 16-byte records
-                surv[(rank & 3) * (CHUNK / 4) + (rank >> 2)] = (unsigned short)(j * 16);
-            }
-            nsurv += __popcll(mask);
-        }
-        {   // pad to a whole number of two-survivor passes of all four slices with the sentinel slot
-            const int rank = nsurv + lane;
-            if (lane < 8 && rank < ((nsurv + 7) & ~7)) surv[(rank & 3) * (CHUNK / 4) + (rank >> 2)] = (unsigned short)(CHUNK * 16);
-        }
-        // same wavefront wrote and now reads `surv`: LDS ops of one wave complete in order; the wave
-        // barrier only stops the compiler from moving the reads above the writes
-        __builtin_amdgcn_wave_barrier();
+        const int nsurv = cull_compact(A, lane, f_xmin, f_xmax, f_ymin, f_ymax, m, cut_k, cut_0, s_geo, s_zid, surv);
         if (base == 0) FT_MARK(3);
         FT_ACC(ft_surv, nsurv);
         // ---- test + insert: lane (pixel, slice) takes survivors slice, slice+4, ...; two per pass so that the LDS
@@ -1463,23 +1587,22 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const unsigned long long ekey = ek[u];
-                const float ez = __uint_as_float((unsigned)(ekey >> 32));
+                const float ez = key_depth(ekey);
                 const float dx = xf - ge[u].x;
                 const float dy = yf - ge[u].y;
-                // rasterize_points.cu:92-101, same expression order (no FMA contraction)
-                const float qval = el[u].x * dx * dx + el[u].y * dx * dy + el[u].z * dy * dy;
+                const float qval = ewa_q(el[u].x, el[u].y, el[u].z, dx, dy);
                 const bool hit = (int)!(fabsf(dx) > ge[u].z) & (int)!(fabsf(dy) > ge[u].w) & (int)!(qval > el[u].w);
                 // A hit can only reach the output if it beats this lane's current K-th entry AND lies within
                 // the depth-merge threshold of the nearest entry seen so far (the final nearest is never
                 // farther, so dropping it now is exact: rasterize_points.cu:586-595 would drop it later).  An empty
                 // list has the NaN pattern in the place of the nearest depth: the comparison is false, as it has to be.
-                const float znear_now = __uint_as_float((unsigned)(key[0] >> 32));
+                const float znear_now = key_depth(key[0]);
                 const bool useful = (int)hit & (int)(ekey < key[KMAX - 1]) & (int)!(ez - znear_now > A.thr);
                 if (__ballot(useful) != 0ull) klist_insert<KMAX>(key, ekey, useful);
             }
         }
         if (base + step < count) {   // (wave-uniform) more chunks follow: refresh the footprint's depth cut
-            unsigned hk = (unsigned)(key[KMAX - 1] >> 32), h0 = (unsigned)(key[0] >> 32);
+            unsigned hk = key_depth_bits(key[KMAX - 1]), h0 = key_depth_bits(key[0]);
             hk = min(hk, dpp_u32<0xB1>(hk)); h0 = min(h0, dpp_u32<0xB1>(h0));     // the pixel's four slices (quad_perm)
             hk = min(hk, dpp_u32<0x4E>(hk)); h0 = min(h0, dpp_u32<0x4E>(h0));
             hk = max(hk, dpp_u32<0x124>(hk)); h0 = max(h0, dpp_u32<0x124>(h0));   // the row's four pixels (row_ror:4, :8)
@@ -1536,14 +1659,14 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
     const bool in_px = (c_e < S) && (lr_e < g.rows);   // the quad's pixel lies inside the image / band
     const bool in_img = owner && in_px;
     // depth merge (rasterize_points.cu:586-595: stop at the first k with z[k] - z[0] > thr), evaluated by every lane
-    const float z0 = __uint_as_float((unsigned)(key[0] >> 32));
+    const float z0 = key_depth(key[0]);
     const bool any = key[0] != KEY_EMPTY;
     unsigned alive_bits = 0;
     {
         bool alive = any;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
-            const float z = __uint_as_float((unsigned)(key[k] >> 32));
+            const float z = key_depth(key[k]);
             alive = alive && (key[k] != KEY_EMPTY) && !(z - z0 > E.thr) && (k < K);
             alive_bits |= (alive ? 1u : 0u) << k;
         }
@@ -1559,6 +1682,7 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
         for (int jj = 0; jj < 4; ++jj)
             if (4 * m + jj < KMAX) kk = (j4 == jj) ? key[4 * m + jj] : kk;
         const bool live = in_px && ((alive_bits >> (4 * m + j4)) & 1u) && (4 * m + j4 < KMAX);
+        // key_id / key_depth written out: as calls in the arms of a select they cost fine_kernel<2..4, *> 4 to 40 instructions
         mi[m] = live ? (int)(unsigned)(kk & 0xffffffffull) : -1;
         mz[m] = live ? __uint_as_float((unsigned)(kk >> 32)) : -1.0f;
         mq[m] = -1.0f;
@@ -1569,61 +1693,7 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
     float wk[MQ];
     float cum = 0.0f;
     if (PACKED) {
-        // records of the lane's fragments: {px,py,..} {a,b,c,..} for Q and {scaler,f0,f1,f2} for the blend, one round trip
-        float2 gp[MQ];
-        float4 ge[MQ], br[MQ];
-#pragma unroll
-        for (int m = 0; m < MQ; ++m) {
-            gp[m] = make_float2(0.f, 0.f);
-            ge[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-            br[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (mi[m] >= 0) {
-                const float4 *R = E.rec + 4 * (size_t)mi[m];
-                gp[m] = *reinterpret_cast<const float2 *>(R);
-                ge[m] = R[1];
-                br[m] = R[2];
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < MQ; ++m) {
-            wk[m] = 0.0f;
-            if (mi[m] >= 0) {
-                const float dx = xf_e - gp[m].x;
-                const float dy = yf_e - gp[m].y;
-                mq[m] = ge[m].x * dx * dx + ge[m].y * dx * dy + ge[m].z * dy * dy;  // rasterize_points.cu:92-101
-                if (E.visible) E.visible[mi[m]] = 1;
-                wk[m] = ewa_weight(mq[m], br[m].x);
-                cum += wk[m];
-            }
-        }
-        // fused blend (same arithmetic and order as blend_forward_kernel): w = exp(-q/2) * scaler, img = sum f * (w / cum)
-        cum += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(cum), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-        cum += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(cum), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-        if (cum < 1e-4f) cum = 1e-4f;
-        const float inv_cum = fast_rcp(cum);
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-#pragma unroll
-        for (int m = 0; m < MQ; ++m) {
-            if (mi[m] >= 0) {
-                const float wn = wk[m] * inv_cum;
-                a0 += br[m].y * wn;
-                a1 += br[m].z * wn;
-                a2 += br[m].w * wn;
-            }
-        }
-        a0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a0), 0xB1, 0xf, 0xf, true));
-        a1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a1), 0xB1, 0xf, 0xf, true));
-        a2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a2), 0xB1, 0xf, 0xf, true));
-        a0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a0), 0x4E, 0xf, 0xf, true));
-        a1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a1), 0x4E, 0xf, 0xf, true));
-        a2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a2), 0x4E, 0xf, 0xf, true));
-        if (in_img) {
-            E.occ[pix] = any ? 1.0f : 0.0f;
-            E.wsum[pix] = cum;
-            float *o = E.image + (size_t)n * E.img_sn + (size_t)lr_e * E.img_sr + (size_t)c_e * 4;
-            // RGBA as ONE 16-byte store per pixel (four dword stores at a 16-byte stride quadruple the write requests)
-            *reinterpret_cast<float4 *>(o) = make_float4(a0, a1, a2, any ? 1.0f : 0.0f);
-        }
+        epilogue_packed<MQ>(&E, xf_e, yf_e, in_img, pix, n, lr_e, c_e, any, mi, mq);
     } else {
         // separate per-point arrays (no packed records: another channel count, the lean workspace, or no fused blend)
 #pragma unroll
@@ -1633,6 +1703,8 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
                 const size_t q = (size_t)mi[m];
                 const float dx = xf_e - E.points[3 * q];
                 const float dy = yf_e - E.points[3 * q + 1];
+                // ewa_q written out: as arguments the three loads are issued in front of the products, not between them
+                // (fine_kernel<2..4, false>: up to 40 instructions more)
                 mq[m] = E.ellipse[3 * q] * dx * dx + E.ellipse[3 * q + 1] * dx * dy + E.ellipse[3 * q + 2] * dy * dy;
                 if (E.visible) E.visible[q] = 1;
                 if (blend) {
@@ -1643,8 +1715,7 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
         }
         if (in_img) E.occ[pix] = any ? 1.0f : 0.0f;
         if (blend) {
-            cum += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(cum), 0xB1, 0xf, 0xf, true));
-            cum += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(cum), 0x4E, 0xf, 0xf, true));
+            cum = quad_sum(cum);
             if (cum < 1e-4f) cum = 1e-4f;
             const float inv_cum = fast_rcp(cum);
             if (in_img) E.wsum[pix] = cum;
@@ -1654,8 +1725,7 @@ __device__ __forceinline__ void fine_tile(const FineArgs &A_entry, const int til
 #pragma unroll
                 for (int m = 0; m < MQ; ++m)
                     if (mi[m] >= 0) acc += E.feat[(size_t)mi[m] * E.C + ch] * (wk[m] * inv_cum);
-                acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xf, 0xf, true));
-                acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xf, 0xf, true));
+                acc = quad_sum(acc);
                 if (in_img) o[ch] = acc;
             }
             if (in_img) o[E.C] = any ? 1.0f : 0.0f;
@@ -1836,9 +1906,9 @@ __global__ __launch_bounds__(64) void fine_generic_kernel(const FineArgs A)
         const float dx = xf - A.points[3 * p];
         const float dy = yf - A.points[3 * p + 1];
         if (fabsf(dx) > A.radii[2 * p] || fabsf(dy) > A.radii[2 * p + 1]) return;
-        const float qval = A.ellipse[3 * p] * dx * dx + A.ellipse[3 * p + 1] * dx * dy + A.ellipse[3 * p + 2] * dy * dy;
+        const float qval = ewa_q(A.ellipse[3 * p], A.ellipse[3 * p + 1], A.ellipse[3 * p + 2], dx, dy);
         if (qval > A.cutoff[p]) return;
-        const unsigned long long ekey = ((unsigned long long)__float_as_uint(pz + 0.0f) << 32) | (unsigned long long)(unsigned)p;
+        const unsigned long long ekey = frag_key(pz + 0.0f, (unsigned)p);
         if (cnt == K && !(ekey < key[K - 1])) return;
         int pos = (cnt < K) ? cnt : K - 1;
         while (pos > 0 && ekey < key[pos - 1]) {
@@ -1861,18 +1931,18 @@ __global__ __launch_bounds__(64) void fine_generic_kernel(const FineArgs A)
     if (c >= S || lr >= g.rows) return;
     const size_t pix = ((size_t)n * g.rows + lr) * S + c;
     A.occ[pix] = cnt > 0 ? 1.0f : 0.0f;
-    const float z0 = cnt > 0 ? __uint_as_float((unsigned)(key[0] >> 32)) : 0.0f;
+    const float z0 = cnt > 0 ? key_depth(key[0]) : 0.0f;
     bool alive = cnt > 0;
     for (int k = 0; k < K; ++k) {
         float z = -1.0f, qv = -1.0f;
         int id = -1;
         if (alive && k < cnt) {
-            z = __uint_as_float((unsigned)(key[k] >> 32));
+            z = key_depth(key[k]);
             if (z - z0 > A.thr) {
                 alive = false;
                 z = -1.0f;
             } else {
-                id = (int)(unsigned)(key[k] & 0xffffffffull);
+                id = key_id(key[k]);
                 qv = kq[k];
                 if (A.visible) A.visible[id] = 1;
             }

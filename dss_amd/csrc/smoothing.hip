@@ -22,8 +22,7 @@ namespace dss {
 // Sum over the 8 lanes of a group, in every lane of the group.
 __device__ __forceinline__ float group8_sum(float v)
 {
-    v += dpp_f32<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_f32<0x4E>(v);    // quad_perm [2,3,0,1]
+    v = quad_sum(v);
     v += dpp_f32<0x141>(v);   // row_half_mirror: lane i <-> lane 7 - i of each 8
     return v;
 }

@@ -1,8 +1,8 @@
 """fp64 CPU reference of the forward blend (TEST INFRASTRUCTURE; plain numpy, no product code in the formulas).
 
 What `ops.blend_forward` (`blend_forward_kernel`, `dss_amd/csrc/blend.hip`) and the fused epilogues of the fine pass
-(`fine_tile`, `dss_amd/csrc/raster_forward.hip`: the packed-record one of `dss_render_forward` at K <= 8 and C = 3, the
-per-point-array one everywhere else and in `dss_splat_fine_blend`) compute, each ENTRY with the sum of its ABSOLUTE terms
+(`dss_amd/csrc/raster_forward.hip`: `epilogue_packed`, the packed-record one of `dss_render_forward` at K <= 8 and C = 3, and
+the per-point-array one inside `fine_tile`, everywhere else and in `dss_splat_fine_blend`) compute, each ENTRY with the sum of its ABSOLUTE terms
 next to it.  Per pixel with the fragment slots k < K, a slot live when idx_k >= 0:
 
     w_k    = exp(-q_k / 2) scaler[idx_k]                 (live slots; 0 otherwise)

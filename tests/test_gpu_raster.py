@@ -263,6 +263,62 @@ def test_cell_ordered_binning_of_large_inputs_is_exact(dist):
         assert torch.equal(fb["idx"], f["idx"][:, own]) and torch.equal(fb["qvalue"], f["qvalue"][:, own]), part.describe()
 
 
+@pytest.mark.parametrize("K,C", [(12, 3), (5, 5)])
+def test_cell_ordered_binning_without_packed_records_is_exact(K, C):
+    """The cell-ordered path (> 2M splats) where the fine pass has no packed records to stage from -- more than 8 fragments per
+    pixel, or another channel count than 3: a list entry is a POSITION of the point order and is translated through `sort_id`
+    before the per-point arrays are read (raster_forward.hip `fine_tile`, "cell-ordered path without packed records"), and the
+    epilogue blends from the separate arrays.  Same fragments as the direct binning of `splat_points` and the stand-alone blend's
+    image, bit for bit.  S = 64: the smallest image that keeps the scene's shape; the sub-lists overflow into the pool."""
+    pts, nrm = scenes.load_cloud("yoga6")
+    pts = scenes.normalize_unit_sphere(pts)
+    pts, nrm = scenes.upsample_jitter(pts, nrm, 106, seed=0)     # 1,057,774 points per cloud, two clouds
+    h = scenes.global_h(pts[::40]) / 40.0
+    S, thr = 64, 0.05
+    M = np.concatenate([scenes.camera_matrices(2.0, 20.0, a)[0] for a in (30.0, 170.0)])
+    V = np.concatenate([scenes.camera_matrices(2.0, 20.0, a)[1] for a in (30.0, 170.0)])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    Pc = len(pts)
+    assert 2 * Pc > 2_000_000
+    first = torch.tensor([0, Pc], dtype=torch.int64, device=DEV)
+    num = torch.tensor([Pc, Pc - 1000], dtype=torch.int64, device=DEV)     # the last 1000 packed points belong to no cloud
+    feat = torch.rand((2 * Pc, C), device=DEV)
+    f = ops.render_forward(t(pts), t(nrm), torch.full((2,), float(h), device=DEV), t(M), t(V), torch.full((2,), 0.1, device=DEV),
+                           torch.full((2,), 100.0, device=DEV), first, num, feat, S, K, 1.0, thr, 1.0, False, True)
+    want = ops.splat_points(f["pts_screen"], f["ellipse_params"], f["cutoff_threshold"], f["radii"], first, num, thr, S, K,
+                            return_visible=True)
+    assert float(want[3].mean()) > 0.005
+    assert int((want[0][..., min(K, 9) - 1] >= 0).sum()) > 0, "some pixel is meant to hold a fragment in the last slot checked"
+    for k, w_ in zip(("idx", "zbuf", "qvalue", "occupancy", "visible"), want):
+        assert torch.equal(f[k], w_), (k, K, C)
+    img, wsum = ops.blend_forward(want[0], want[2], want[3], f["scaler"], feat, return_wsum=True)
+    assert f["image"].shape[-1] == C + 1
+    assert torch.equal(f["image"], img) and torch.equal(f["wsum"], wsum), (K, C)
+
+
+@pytest.mark.parametrize("K,C", [(5, 3), (12, 3), (5, 5)])
+def test_render_forward_without_the_depth_plane_gives_the_same_other_outputs(K, C):
+    """`want_zbuf=False` (the training step: the fused backward never reads depths) hands the fine pass no depth plane: the LDS
+    transpose skips it in its three-plane form (K <= 8) and in its one-plane form (K = 12).  `zbuf` is None and every other
+    output has the bits of the call with depths; S = 100 leaves a ragged last tile column and row."""
+    pts, nrm = scenes.load_cloud("bunny")
+    pts = scenes.normalize_unit_sphere(pts)
+    h = scenes.global_h(pts)
+    S, thr = 100, 0.05
+    M, V, _ = scenes.camera_matrices(2.0, 20.0, 30.0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    P = pts.shape[0]
+    a = (t(pts), t(nrm), torch.full((1,), h, device=DEV), t(M), t(V), torch.full((1,), 0.1, device=DEV),
+         torch.full((1,), 100.0, device=DEV), torch.zeros(1, dtype=torch.int64, device=DEV),
+         torch.full((1,), P, dtype=torch.int64, device=DEV), torch.rand((P, C), device=DEV))
+    ref = ops.render_forward(*a, S, K, 1.0, thr, 1.0, False, True)
+    got = ops.render_forward(*a, S, K, 1.0, thr, 1.0, False, True, want_zbuf=False)
+    assert got["zbuf"] is None and ref["zbuf"] is not None
+    assert float(ref["occupancy"].mean()) > 0.05
+    for k in ("idx", "qvalue", "occupancy", "visible", "image", "wsum"):
+        assert torch.equal(ref[k], got[k]), (k, K, C)
+
+
 def test_cell_ordered_binning_keeps_overflowing_wide_splats_on_the_lists():
     """The cell-ordered path (> 2M splats) with WIDE splats among them: 1 % of the points get a variance scale 4000x the cloud's
     (20-40 pixel splats, part of them wider than 8 x 8 tiles), sub-lists overflow under them, and `bin_sorted_kernel` records their full
