@@ -47,4 +47,7 @@ def __getattr__(name):
     if name in _CLOUD_OPS:
         from . import cloud_ops
         return getattr(cloud_ops, name)
+    if name == "evaluate_cloud":   # the reference's evaluation row (dss_amd/evaluation.py), imported on first use likewise
+        from .evaluation import evaluate_cloud
+        return evaluate_cloud
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

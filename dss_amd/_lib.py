@@ -97,6 +97,13 @@ SIGNATURES = {
     "dss_nearest_workspace": (_c_sz, [_c_int, _c_i64]),
     "dss_nearest_points": (_c_int, [_c_vp] * 3 + [_c_i64] + [_c_vp] * 3 + [_c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "dss_chamfer_backward": (_c_int, [_c_vp] * 4 + [_c_i64, _c_vp, _c_vp, _c_i64, _c_int] + [_c_vp] * 8 + [_c_vp]),
+    "dss_point_face_workspace": (_c_sz, [_c_int, _c_i64]),
+    "dss_point_face_distance": (_c_int, [_c_vp] * 3 + [_c_i64, _c_vp, _c_i64] + [_c_vp] * 3 + [_c_i64, _c_int, _c_vp, _c_vp, _c_vp,
+                                                                                              _c_sz, _c_vp]),
+    "dss_face_point_distance": (_c_int, [_c_vp] * 3 + [_c_i64, _c_vp, _c_i64] + [_c_vp] * 3 + [_c_i64, _c_int, _c_vp, _c_vp, _c_vp,
+                                                                                              _c_sz, _c_vp]),
+    "dss_mesh_distance_backward": (_c_int, [_c_vp] * 3 + [_c_i64, _c_vp, _c_i64] + [_c_vp] * 3 + [_c_i64, _c_int] + [_c_vp] * 8
+                                   + [_c_vp]),
     "dss_upsample_candidates": (_c_int, [_c_vp] * 4 + [_c_int, _c_i64, _c_int] + [_c_vp] * 3 + [_c_vp]),
     "dss_upsample_insert": (_c_int, [_c_vp, _c_vp, _c_int] + [_c_vp] * 8 + [_c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp,
                                                                            _c_vp]),
@@ -150,6 +157,7 @@ def load():
 WS_ORDER_SAVE, WS_ORDER_REUSE = 0x10, 0x20   # include/dss_hip.h DSS_WS_ORDER_* (flags of workspace_state)
 WS_BAND_OUTPUTS = 0x40   # DSS_WS_BAND_OUTPUTS: ellipse / scaler / cutoff only for the splats that meet the row band
 OPT_LEAN_WORKSPACE, OPT_BACKWARD_TPW, OPT_BACKWARD_ADDR64, OPT_BACKWARD_FUSED, OPT_KNN_QUERY, OPT_BACKWARD_GRID = 0, 1, 2, 3, 4, 5   # include/dss_hip.h DSS_OPT_*
+OPT_MESH_LARGE = 6
 
 
 def set_option(option: int, value: int) -> int:

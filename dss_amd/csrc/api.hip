@@ -90,6 +90,10 @@ extern "C" int dss_set_option(int option, int value)
         dss::set_error("dss_set_option: DSS_OPT_BACKWARD_GRID takes 0 (automatic) or a positive number of workgroups");
         return DSS_ERR_INVALID_ARGUMENT;
     }
+    if (option == DSS_OPT_MESH_LARGE && (value < 0 || value > 4096)) {
+        dss::set_error("dss_set_option: DSS_OPT_MESH_LARGE takes 0 (default) or 1 .. 4096 quarters of a cell");
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
     dss::g_opt[option].store(value, std::memory_order_relaxed);
     return DSS_OK;
 }

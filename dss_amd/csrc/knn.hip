@@ -1811,6 +1811,58 @@ __device__ __forceinline__ int nearest_start_cell(float v, float mn, float inv_c
     return (int)fminf(fmaxf(floorf((v - mn) * inv_cell), 0.0f), (float)(res - 1));
 }
 
+// What the cross walks share, stated once for point_face_query and face_point_query.  nearest_query_kernel below keeps its
+// own written-out copy of the same rules: routed through these functions it compiles to 78 instead of 70 VGPRs (six
+// instead of seven wavefronts per SIMD), and no existing kernel is to change with this section.
+// The searcher is a box [lo, hi] per axis (a query point: lo == hi).  tol: the rounding allowance of one axis; o2: the
+// squared distance of the searcher to the grid's box along each axis, rounded down (see the exactness note above).
+struct CrossGap { float tolx, toly, tolz, ox2, oy2, oz2; };
+__device__ __forceinline__ CrossGap cross_gap(const KnnGrid &g, float span, float lox, float hix, float loy, float hiy, float loz, float hiz)
+{
+    CrossGap t;
+    t.tolx = 1e-6f * (span + fmaxf(fabsf(lox), fabsf(hix)) + fabsf(g.minx));
+    t.toly = 1e-6f * (span + fmaxf(fabsf(loy), fabsf(hiy)) + fabsf(g.miny));
+    t.tolz = 1e-6f * (span + fmaxf(fabsf(loz), fabsf(hiz)) + fabsf(g.minz));
+    const float ox = fmaxf(fmaxf(g.minx - hix, lox - (g.minx + span)) - t.tolx, 0.0f);
+    const float oy = fmaxf(fmaxf(g.miny - hiy, loy - (g.miny + span)) - t.toly, 0.0f);
+    const float oz = fmaxf(fmaxf(g.minz - hiz, loz - (g.minz + span)) - t.tolz, 0.0f);
+    t.ox2 = ox * ox; t.oy2 = oy * oy; t.oz2 = oz * oz;
+    return t;
+}
+// Squared distance from the searcher to everything outside the visited block of cells [x0, x1] x [y0, y1] x [z0, z1]
+// (already cut at the grid's sides): the smallest over the block's open faces; +inf when no face is open.
+__device__ __forceinline__ float cross_unvisited_b2(const KnnGrid &g, int res, const CrossGap &t, int x0, int x1, int y0, int y1, int z0,
+                                                    int z1, float lox, float hix, float loy, float hiy, float loz, float hiz)
+{
+    float b2 = __builtin_huge_valf();
+    if (x0 > 0) { const float d = fmaxf(lox - (g.minx + (float)x0 * g.cell) - t.tolx, 0.0f); b2 = fminf(b2, d * d + t.oy2 + t.oz2); }
+    if (x1 < res - 1) { const float d = fmaxf((g.minx + (float)(x1 + 1) * g.cell) - hix - t.tolx, 0.0f); b2 = fminf(b2, d * d + t.oy2 + t.oz2); }
+    if (y0 > 0) { const float d = fmaxf(loy - (g.miny + (float)y0 * g.cell) - t.toly, 0.0f); b2 = fminf(b2, d * d + t.ox2 + t.oz2); }
+    if (y1 < res - 1) { const float d = fmaxf((g.miny + (float)(y1 + 1) * g.cell) - hiy - t.toly, 0.0f); b2 = fminf(b2, d * d + t.ox2 + t.oz2); }
+    if (z0 > 0) { const float d = fmaxf(loz - (g.minz + (float)z0 * g.cell) - t.tolz, 0.0f); b2 = fminf(b2, d * d + t.ox2 + t.oy2); }
+    if (z1 < res - 1) { const float d = fmaxf((g.minz + (float)(z1 + 1) * g.cell) - hiz - t.tolz, 0.0f); b2 = fminf(b2, d * d + t.ox2 + t.oy2); }
+    return b2;
+}
+// The cells that grow the visited block from `old` to `now` (both cut at the grid's sides; old empty: x1 < x0), as ranges
+// of the cell-sorted array: cells consecutive along x are consecutive in memory, so a row outside the old block is ONE
+// range, and a row that crosses it contributes the cells in front of and behind it.
+struct CellBlock { int x0, x1, y0, y1, z0, z1; };
+template <typename Visit>
+__device__ __forceinline__ void cross_visit_shell(const uint32_t *__restrict__ off, int res, const CellBlock &old, const CellBlock &now,
+                                                  Visit visit)
+{
+    for (int z = now.z0; z <= now.z1; ++z)
+        for (int y = now.y0; y <= now.y1; ++y) {
+            const int c = (z * res + y) * res;
+            if (z < old.z0 || z > old.z1 || y < old.y0 || y > old.y1) {
+                visit(off[c + now.x0], off[c + now.x1 + 1]);
+            } else {
+                if (now.x0 < old.x0) visit(off[c + now.x0], off[c + old.x0]);
+                if (now.x1 > old.x1) visit(off[c + old.x1 + 1], off[c + now.x1 + 1]);
+            }
+        }
+}
+
 __global__ __launch_bounds__(256) void nearest_query_kernel(const float *__restrict__ x, const int64_t *__restrict__ x_first,
                                                             const int64_t *__restrict__ x_num, int64_t Px,
                                                             const int64_t *__restrict__ y_first, const int64_t *__restrict__ y_num,
@@ -2012,5 +2064,681 @@ extern "C" int dss_chamfer_backward(const float *x, const float *y, const int64_
     if (blocks > 0x7fffffffll) { set_error("%s: too many points", who); return DSS_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(chamfer_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, y, x_first, x_num, Px,
                        y_first, y_num, Py, N, idx_xy, idx_yx, order_xy, order_yx, gx, gy, grad_x, grad_y);
+    return check_launch(who);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Point-to-mesh distance (dss_point_face_distance, dss_face_point_distance, dss_mesh_distance_backward): the p2f columns
+// of the reference's evaluation row (scripts/evaluatePointClouds.py:52,103-132) and the surface term
+// pytorch3d.loss.point_mesh_face_distance.  Cloud n is measured against mesh n.  The code lives in this file because
+// both searches use build_grid as it stands (file-static): over the triangles' centroids one way, over the points the
+// other.
+//
+// The distance (mesh_d2), fp32, no contraction, correctly rounded division, dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z:
+//   seg(q, P, R): p0 = the lexicographically smaller endpoint (x, then y, then z, by value), e = p1 - p0, w = q - p0,
+//       ee = dot(e, e), we = dot(w, e);  we <= 0 or ee == 0: r = w;  we >= ee: r = q - p1;  else t = we / ee, r = w - t e;
+//       result dot(r, r)
+//   interior: e0 = B - A, e1 = C - A, n = e0 x e1, nn = dot(n, n); for A->B, B->C, C->A: s = dot((R - P) x (q - P), n);
+//       inside = nn > 0 and all three s > 0;  plane = (h h) / nn, h = dot(q - A, n)
+//   d2 = the first minimum under `<` of seg(A,B), seg(B,C), seg(C,A), inside ? plane : +inf, starting from +inf: a NaN
+//       never wins.  An edge shared by two faces gives both the same bits (its endpoints are ordered by position, not by
+//       the face's winding), so "ties go to the smaller face id" is meaningful; a degenerate triangle is the union of its
+//       edges without any threshold.
+//
+// No face id outside [0, F) and no vertex id outside [0, V) reaches a load: mesh_load_face is the ONLY function that reads
+// `verts` through `faces`; it is called with 0 <= f < F (every caller checks, stated at the call), reads the three ids of
+// row f, and returns false BEFORE any vertex load when one of them is outside [0, V); it also returns false for a face
+// with a non-finite vertex.  A face it refuses is ABSENT: its centroid is written as NaN (knn_box_reduce passes NaN over,
+// so the grid's box does not see it; knn_cell_of clamps whatever cell a NaN converts to into the grid), its radius as -1,
+// its record in cell order carries radius -1 and no vertex, and the large list never receives it.
+//
+// The error of mesh_d2 against the exact distance D.  The segment terms lose c eps (D^2 + L D + eps L^2), L = D + longest
+// edge, eps = 2^-23 (the middle term is the cancellation in w - t e).  The PLANE term is worse conditioned: n = e0 x e1 is
+// a difference of products of size |e0| |e1|, so its direction is off by eps kappa, kappa = (longest edge)^2 / |n| (1 for
+// an equilateral-ish triangle, ~aspect for a sliver); h = dot(q - A, n) and the three side tests inherit that, and a
+// query a wrongly signed side test lets into the plane branch is within eps kappa |q - A| of the edge.  Together
+//     |d2 - D^2| <= E(D) = c eps kappa (D^2 + L D + eps kappa L^2)
+// with c <= 1 measured on every scene of tests/test_mesh_distance_cpu.py, slivers of aspect 1 to 1e6 sampled ABOVE THEIR
+// INTERIORS included (without kappa the same samples give c = 12 at aspect 100 and 1e4 at aspect 1e4); c = 8 is taken
+// below.  mesh_kappa computes kappa in fp32 with the operations of mesh_d2's own nn: nn == 0 means the plane branch is
+// never taken (kappa = 1); an nn too small to carry its digits counts as unbounded.
+//
+// Point -> face.  mesh_prep writes, per face, the centroid c = ((A + B) + C) / 3, the radius R_f >= max |vertex - c|
+// (rounded up) and kappa_f; build_grid sorts the centroids; mesh_classify sends the faces with R_f > mult * cell, and the
+// faces with kappa_f > MESH_KAPPA_MAX, to their mesh's LARGE LIST (length counted on the device, never read by the host)
+// and takes R_grid = max R_f and K_grid = max kappa_f of the others; mesh_gather writes the nine floats of every face in
+// CELL ORDER (48 bytes per face: three float4 with radius and id) so that the walk reads records, not indices.  A face of
+// the large list keeps its centroid in the grid (classification needs the cell size, so it comes after the build): its
+// record carries radius -2 and the walk passes it over; one huge triangle therefore stretches the centroids' box only by
+// its centroid, not by its vertices.  The query is nearest_query_kernel's ring walk (clamped start cell, `o` terms, tol),
+// over centroids.  Exactness: after a ring, every unvisited centroid is at least b away from q (the argument above
+// nearest_query_kernel, b2 = b^2 computed there); its triangle lies within R_grid of the centroid, so its true distance is
+// D >= lim = b - R_grid, and its computed d2 >= D^2 - E(D) with kappa <= K_grid and longest edge <= 2 R_grid.
+// D^2 - E(D) grows with D once D > c eps kappa R_grid, so with
+//     floor = lim^2 - 2e-6 K (lim + 2 R_grid)^2,   lim = 0.999999 sqrt(b2) - R_grid  (R_grid carries its own 1e-6 inflation)
+// every unvisited triangle computes d2 >= floor: 2e-6 K s^2 = 16.8 eps K s^2 >= 8 eps K (2 lim^2 + 2 R lim + eps K s^2) as
+// long as 8 eps K <= 0.8, and beyond that 2e-6 K >= 1 makes the floor negative.  For lim below c eps K R_grid the floor is
+// negative too and nothing stops.  The walk stops at best < floor, strictly: an unvisited triangle neither beats the result
+// nor ties with it.  The same floor, from a candidate's own centroid distance, rejects it before its record is loaded.
+// Faces of the large list are tested by every query of the mesh, by brute force, whatever their kappa.  Among everything
+// tested the order is (d2, face id).
+//
+// Face -> point.  The cloud's ordinary point grid; one WAVEFRONT per triangle (candidate counts differ by orders of
+// magnitude: two triangles under 100,000 points is legal input), lanes stride the candidates of a row of cells, one
+// cross-lane (d2, id) minimum at the end.  Ring 0 is the block of cells the triangle's bounding box covers (clamped),
+// ring r grows it by r cells on every side.  An unvisited point lies in a cell beyond an open side of the block -- low
+// x: x < F = minx + X0 cell -- and inside the grid's box on the other axes; the triangle lies inside its bounding box;
+// so their distance is at least sqrt(gap^2 + oy^2 + oz^2), gap = box.lo.x - F, o = distance between the triangle's box
+// and the grid's box along that axis, each reduced by tol first as in nearest_query_kernel.  floor as above with
+// lim = 0.999999 sqrt(b2), the longest edge bounded by the box diagonal and K = the wavefront's own triangle's kappa: a
+// sliver of kappa above 5e5 never stops early and compares with every point of its cloud.
+// ---------------------------------------------------------------------------------------------------------------
+namespace dss {
+
+struct MeshTri { float ax, ay, az, bx, by, bz, cx, cy, cz; };
+
+__device__ __forceinline__ bool mesh_finite(float v) { return fabsf(v) < __builtin_huge_valf(); }
+
+// The one reader of vertices through face ids.  REQUIRES 0 <= f < F.
+__device__ __forceinline__ bool mesh_load_face(int64_t f, const int64_t *__restrict__ faces, const float *__restrict__ verts,
+                                               int64_t V, MeshTri &t)
+{
+    const int64_t ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
+    if ((uint64_t)ia >= (uint64_t)V || (uint64_t)ib >= (uint64_t)V || (uint64_t)ic >= (uint64_t)V) return false;
+    t.ax = verts[3 * ia]; t.ay = verts[3 * ia + 1]; t.az = verts[3 * ia + 2];
+    t.bx = verts[3 * ib]; t.by = verts[3 * ib + 1]; t.bz = verts[3 * ib + 2];
+    t.cx = verts[3 * ic]; t.cy = verts[3 * ic + 1]; t.cz = verts[3 * ic + 2];
+    return mesh_finite(t.ax) && mesh_finite(t.ay) && mesh_finite(t.az) && mesh_finite(t.bx) && mesh_finite(t.by) && mesh_finite(t.bz) &&
+           mesh_finite(t.cx) && mesh_finite(t.cy) && mesh_finite(t.cz);
+}
+
+// The arithmetic of the distance, once, for float (the searches) and double (the backward's closest point)
+template <typename T>
+__device__ __forceinline__ T mesh_dot(T ax, T ay, T az, T bx, T by, T bz) { return (ax * bx + ay * by) + az * bz; }
+
+// seg(q, P, R) -> squared distance; t_out = parameter along p0 -> p1, swapped = (p0 is R)
+template <typename T>
+__device__ __forceinline__ T mesh_seg(T qx, T qy, T qz, T px, T py, T pz, T rx, T ry, T rz, T &t_out, bool &swapped)
+{
+    const bool sw = (rx < px) | ((rx == px) & ((ry < py) | ((ry == py) & (rz < pz))));
+    const T p0x = sw ? rx : px, p0y = sw ? ry : py, p0z = sw ? rz : pz;
+    const T p1x = sw ? px : rx, p1y = sw ? py : ry, p1z = sw ? pz : rz;
+    const T ex = p1x - p0x, ey = p1y - p0y, ez = p1z - p0z;
+    const T wx = qx - p0x, wy = qy - p0y, wz = qz - p0z;
+    const T ee = mesh_dot(ex, ey, ez, ex, ey, ez), we = mesh_dot(wx, wy, wz, ex, ey, ez);
+    T rx_, ry_, rz_, t;
+    if ((we <= (T)0) | (ee == (T)0)) { rx_ = wx; ry_ = wy; rz_ = wz; t = (T)0; }
+    else if (we >= ee) { rx_ = qx - p1x; ry_ = qy - p1y; rz_ = qz - p1z; t = (T)1; }
+    else { t = we / ee; rx_ = wx - t * ex; ry_ = wy - t * ey; rz_ = wz - t * ez; }
+    t_out = t;
+    swapped = sw;
+    return mesh_dot(rx_, ry_, rz_, rx_, ry_, rz_);
+}
+
+// s = dot((R - P) x (q - P), n)
+template <typename T>
+__device__ __forceinline__ T mesh_side(T qx, T qy, T qz, T px, T py, T pz, T rx, T ry, T rz, T nx, T ny, T nz)
+{
+    const T ux = rx - px, uy = ry - py, uz = rz - pz, vx = qx - px, vy = qy - py, vz = qz - pz;
+    return mesh_dot(uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx, nx, ny, nz);
+}
+
+// d2 of the definition; WEIGHTS: also the barycentric weights (wa, wb, wc) of the closest point, of the first minimum
+// in the order AB, BC, CA, plane
+template <typename T, bool WEIGHTS>
+__device__ __forceinline__ T mesh_d2(T qx, T qy, T qz, T ax, T ay, T az, T bx, T by, T bz, T cx, T cy, T cz, T &wa, T &wb, T &wc)
+{
+    const T inf = (T)__builtin_huge_valf();
+    T best = inf;
+    T t0, t1, t2;
+    bool s0, s1, s2;
+    const T dab = mesh_seg(qx, qy, qz, ax, ay, az, bx, by, bz, t0, s0);
+    const T dbc = mesh_seg(qx, qy, qz, bx, by, bz, cx, cy, cz, t1, s1);
+    const T dca = mesh_seg(qx, qy, qz, cx, cy, cz, ax, ay, az, t2, s2);
+    const T e0x = bx - ax, e0y = by - ay, e0z = bz - az, e1x = cx - ax, e1y = cy - ay, e1z = cz - az;
+    const T nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
+    const T nn = mesh_dot(nx, ny, nz, nx, ny, nz);
+    const T sab = mesh_side(qx, qy, qz, ax, ay, az, bx, by, bz, nx, ny, nz);
+    const T sbc = mesh_side(qx, qy, qz, bx, by, bz, cx, cy, cz, nx, ny, nz);
+    const T sca = mesh_side(qx, qy, qz, cx, cy, cz, ax, ay, az, nx, ny, nz);
+    const bool inside = (nn > (T)0) & (sab > (T)0) & (sbc > (T)0) & (sca > (T)0);
+    const T h = mesh_dot(qx - ax, qy - ay, qz - az, nx, ny, nz);
+    const T plane = inside ? (h * h) / nn : inf;
+    int win = -1;
+    if (dab < best) { best = dab; win = 0; }
+    if (dbc < best) { best = dbc; win = 1; }
+    if (dca < best) { best = dca; win = 2; }
+    if (plane < best) { best = plane; win = 3; }
+    if (WEIGHTS) {
+        wa = (T)1; wb = (T)0; wc = (T)0;   // (nothing won: a NaN pair, which no index list names)
+        if (win == 0) { const T u = s0 ? (T)1 - t0 : t0; wa = (T)1 - u; wb = u; wc = (T)0; }          // u = weight of the edge's second vertex
+        if (win == 1) { const T u = s1 ? (T)1 - t1 : t1; wb = (T)1 - u; wc = u; wa = (T)0; }
+        if (win == 2) { const T u = s2 ? (T)1 - t2 : t2; wc = (T)1 - u; wa = u; wb = (T)0; }
+        if (win == 3) { wa = sbc / nn; wb = sca / nn; wc = sab / nn; }   // s of the edge opposite a vertex = its weight * nn
+    }
+    return best;
+}
+
+__device__ __forceinline__ float mesh_d2f(float qx, float qy, float qz, const MeshTri &t)
+{
+    float wa, wb, wc;
+    return mesh_d2<float, false>(qx, qy, qz, t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz, wa, wb, wc);
+}
+
+// Every triangle of kappa <= `kappa` and longest edge <= edge_max whose reference point (its centroid, at most `reach` from
+// its vertices; or the triangle itself, reach = 0) is at least sqrt(b2) away computes d2 >= the returned value (see the
+// exactness note above).  Point -> face: reach = R_grid, edge_max = 2 R_grid, kappa = K_grid; face -> point: 0, the box
+// diagonal, the triangle's own kappa.
+__device__ __forceinline__ float mesh_floor(float b2, float reach, float edge_max, float kappa)
+{
+    const float lim = sqrtf(b2) * 0.999999f - reach;
+    const float s = lim + edge_max;
+    return lim > 0.0f ? lim * lim - (2e-6f * kappa) * (s * s) : -1.0f;
+}
+
+// kappa = (longest edge)^2 / |n| >= 1, rounded up: the conditioning of the plane term (see the error note above).  nn is
+// mesh_d2's own expression, so nn == 0 here means the plane branch is never taken there: kappa = 1.  An nn below 1e-30
+// (triangles a few 1e-8 across) loses digits to underflow: +inf, no bound is claimed.
+__device__ __forceinline__ float mesh_kappa(const MeshTri &t)
+{
+    const float e0x = t.bx - t.ax, e0y = t.by - t.ay, e0z = t.bz - t.az, e1x = t.cx - t.ax, e1y = t.cy - t.ay, e1z = t.cz - t.az;
+    const float e2x = t.cx - t.bx, e2y = t.cy - t.by, e2z = t.cz - t.bz;
+    const float nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
+    const float nn = mesh_dot(nx, ny, nz, nx, ny, nz);
+    const float l2 = fmaxf(fmaxf(mesh_dot(e0x, e0y, e0z, e0x, e0y, e0z), mesh_dot(e1x, e1y, e1z, e1x, e1y, e1z)),
+                           mesh_dot(e2x, e2y, e2z, e2x, e2y, e2z));
+    if (nn == 0.0f) return 1.0f;
+    if (!(nn >= 1e-30f)) return __builtin_huge_valf();
+    const float k = l2 / sqrtf(nn) * 1.01f;
+    return k >= 1.0f ? k : (k == k ? 1.0f : __builtin_huge_valf());
+}
+
+// Faces with R_f above MESH_LARGE_QUARTERS / 4 cells go to the large list (DSS_OPT_MESH_LARGE overrides, for A/B runs:
+// tools/mesh_distance_timing.py).  Any value is exact; it trades the walk's reach R_grid against the list's length.
+#define MESH_LARGE_QUARTERS 8
+// and so do faces whose kappa exceeds this: the walk's floor loses 2e-6 K_grid of (lim + 2 R_grid)^2, and a single sliver
+// must not take that from every query of its mesh
+#define MESH_KAPPA_MAX 256.0f
+#define MESH_ABSENT (-1.0f)   // radius of a face that is not searched through the grid: absent (-1) or on the large list (-2)
+
+// per packed face slot: centroid (NaN when absent / not a grid face) and radius
+__global__ __launch_bounds__(256) void mesh_prep_kernel(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ faces,
+                                                        const int64_t *__restrict__ f_first, const int64_t *__restrict__ f_num, int N,
+                                                        int64_t F, float *__restrict__ cent, float *__restrict__ rf, float *__restrict__ kap)
+{
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    const float nan = __builtin_nanf("");
+    float cx = nan, cy = nan, cz = nan, r = MESH_ABSENT, k = 1.0f;
+    MeshTri t;
+    if (find_cloud(f, f_first, f_num, N) >= 0 && mesh_load_face(f, faces, verts, V, t)) {   // (0 <= f < F)
+        k = mesh_kappa(t);
+        cx = ((t.ax + t.bx) + t.cx) / 3.0f; cy = ((t.ay + t.by) + t.cy) / 3.0f; cz = ((t.az + t.bz) + t.cz) / 3.0f;
+        const float da = mesh_dot(t.ax - cx, t.ay - cy, t.az - cz, t.ax - cx, t.ay - cy, t.az - cz);
+        const float db = mesh_dot(t.bx - cx, t.by - cy, t.bz - cz, t.bx - cx, t.by - cy, t.bz - cz);
+        const float dc = mesh_dot(t.cx - cx, t.cy - cy, t.cz - cz, t.cx - cx, t.cy - cy, t.cz - cz);
+        r = sqrtf(fmaxf(fmaxf(da, db), dc)) * 1.000001f + 1e-30f;   // rounded up, and > 0 (R_grid == 0 means "no grid face")
+        if (!(mesh_finite(cx) && mesh_finite(cy) && mesh_finite(cz) && mesh_finite(r))) {
+            cx = cy = cz = nan;                 // sums that overflow: off the grid, onto the large list
+            r = __builtin_huge_valf();
+        }
+    }
+    cent[3 * f] = cx; cent[3 * f + 1] = cy; cent[3 * f + 2] = cz;
+    rf[f] = r;
+    kap[f] = k;
+}
+
+// after build_grid: large and ill-conditioned faces to their mesh's list, R_grid and K_grid of the others.  per_mesh: (N, 3)
+// ints = {bits of R_grid, length of the large list, bits of K_grid}, zeroed before.  quarter_cells: the multiple, in
+// quarters of a cell.
+__global__ __launch_bounds__(256) void mesh_classify_kernel(const int64_t *__restrict__ f_first, const int64_t *__restrict__ f_num, int N,
+                                                            int64_t F, const KnnGrid *__restrict__ grids, float quarter_cells,
+                                                            float *__restrict__ rf, const float *__restrict__ kap, int *__restrict__ per_mesh,
+                                                            int *__restrict__ large)
+{
+    // (no early return: every lane takes part in the wavefront's reductions below)
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int m = f < F ? find_cloud(f, f_first, f_num, N) : -1;
+    const float r = m >= 0 ? rf[f] : MESH_ABSENT;
+    const float k = m >= 0 ? kap[f] : 1.0f;
+    const bool usable = r >= 0.0f;
+    const bool in_grid = usable && r <= 0.25f * quarter_cells * grids[m].cell && k <= MESH_KAPPA_MAX;
+    // R_grid and K_grid: one pair of atomics per wavefront and mesh among its lanes, not per face (one atomic per face is
+    // F same-address atomics in a row: 1.1 ms each at 100,000 faces, as knn_bbox_kernel found for the box)
+    unsigned long long todo = __ballot(in_grid);
+    while (todo != 0ull) {   // (wave-uniform)
+        const int leader = __builtin_ctzll(todo);
+        const int lm = __shfl(m, leader);
+        const bool mine = in_grid && m == lm;
+        int vr = mine ? __float_as_int(r) : 0, vk = mine ? __float_as_int(k) : 0;   // (r > 0, k >= 1: positive floats order like their bits)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            vr = max(vr, __shfl_xor(vr, o));
+            vk = max(vk, __shfl_xor(vk, o));
+        }
+        if (lane == leader) {
+            atomicMax(&per_mesh[3 * lm], vr);
+            atomicMax(&per_mesh[3 * lm + 2], vk);
+        }
+        todo &= ~__ballot(mine);
+    }
+    if (usable && !in_grid) {
+        // f_first[m] + pos < F: the faces counted here are slots of mesh m below F, and pos counts fewer than all of them
+        // (checked all the same: a negative f_first is merely wrong input, the query kernel refuses such a mesh)
+        const int pos = atomicAdd(&per_mesh[3 * m + 1], 1);
+        const int64_t at = f_first[m] + pos;
+        if ((uint64_t)at < (uint64_t)F) large[at] = (int)f;
+        rf[f] = -2.0f;
+    }
+}
+
+// the faces' vertices in cell order: rec[3 j .. 3 j + 2] = (A, B.x) (B.yz, C.xy) (C.z, radius or -1, packed face id, 0)
+__global__ __launch_bounds__(256) void mesh_gather_kernel(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ faces,
+                                                          const int64_t *__restrict__ f_first, const int64_t *__restrict__ f_num, int N,
+                                                          int64_t F, const float4 *__restrict__ sorted, const float *__restrict__ rf,
+                                                          float4 *__restrict__ rec)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= F) return;
+    if (find_cloud(j, f_first, f_num, N) < 0) return;   // (a slot of no mesh: `sorted` holds nothing there)
+    const int id = __float_as_int(sorted[j].w);
+    MeshTri t = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float r = MESH_ABSENT;
+    if ((uint32_t)id < (uint64_t)F) {                  // (0 <= id < F before rf and mesh_load_face see it)
+        r = rf[id];
+        if (!(r >= 0.0f && mesh_load_face(id, faces, verts, V, t))) r = MESH_ABSENT;
+    }
+    rec[3 * j] = make_float4(t.ax, t.ay, t.az, t.bx);
+    rec[3 * j + 1] = make_float4(t.by, t.bz, t.cx, t.cy);
+    rec[3 * j + 2] = make_float4(t.cz, r, __int_as_float(id), 0.0f);
+}
+
+__global__ __launch_bounds__(256) void point_face_query_kernel(const float *__restrict__ x, const int64_t *__restrict__ p_first,
+                                                               const int64_t *__restrict__ p_num, int64_t P,
+                                                               const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ faces,
+                                                               const int64_t *__restrict__ f_first, const int64_t *__restrict__ f_num,
+                                                               int64_t F, int N, const KnnGrid *__restrict__ grids, size_t stride,
+                                                               const uint32_t *__restrict__ offsets, const float4 *__restrict__ sorted,
+                                                               const float4 *__restrict__ rec, const int *__restrict__ per_mesh,
+                                                               const int *__restrict__ large, float *__restrict__ d2_out,
+                                                               int64_t *__restrict__ idx_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const int n = find_cloud(i, p_first, p_num, N);
+    int64_t f0 = 0, fn = 0;
+    if (n >= 0) { f0 = f_first[n]; fn = f_num[n]; }
+    if (n < 0 || fn <= 0 || f0 < 0 || f0 + fn > F) {   // slot of no cloud (its position is not read), or nothing to search
+        d2_out[i] = 0.0f;
+        idx_out[i] = -1;
+        return;
+    }
+    const float qx = x[3 * i], qy = x[3 * i + 1], qz = x[3 * i + 2];
+    float best = __builtin_huge_valf();
+    int bid = 0x7fffffff;
+    auto consider = [&](const MeshTri &t, int id) __attribute__((always_inline)) {
+        const float d2 = mesh_d2f(qx, qy, qz, t);
+        const bool lt = (d2 < best) | ((d2 == best) & (id < bid));
+        best = lt ? d2 : best;
+        bid = lt ? id : bid;
+    };
+    // the large list first: it seeds `best` for the walk's rejects
+    const int n_large = min(max(per_mesh[3 * n + 1], 0), (int)min(fn, (int64_t)0x7fffffff));
+    for (int k = 0; k < n_large; ++k) {
+        const int f = large[f0 + k];
+        MeshTri t;
+        if ((uint32_t)f < (uint64_t)F && mesh_load_face(f, faces, verts, V, t)) consider(t, f);   // (0 <= f < F)
+    }
+    const float rgrid = __int_as_float(per_mesh[3 * n]), kgrid = __int_as_float(per_mesh[3 * n + 2]);
+    if (rgrid > 0.0f) {   // (0: no face of this mesh is searched through the grid)
+        const KnnGrid g = grids[n];
+        const uint32_t *off = offsets + (size_t)n * stride;
+        const int res = g.res;
+        const int cx = nearest_start_cell(qx, g.minx, g.inv_cell, res);
+        const int cy = nearest_start_cell(qy, g.miny, g.inv_cell, res);
+        const int cz = nearest_start_cell(qz, g.minz, g.inv_cell, res);
+        const CrossGap gap = cross_gap(g, (float)res * g.cell, qx, qx, qy, qy, qz, qz);
+        const float edge_max = 2.0f * rgrid;
+        auto visit = [&](uint32_t s, uint32_t e) __attribute__((always_inline)) {
+            for (uint32_t j = s; j < e; ++j) {
+                const float4 c = sorted[f0 + j];
+                const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
+                // (a NaN centroid -- an absent face, or one whose sums overflowed -- fails this test and is passed over; a face
+                // of the large list has a finite centroid and is passed over by its record's radius below)
+                if (!(mesh_floor((dx * dx + dy * dy) + dz * dz, rgrid, edge_max, kgrid) <= best)) continue;
+                const float4 r0 = rec[3 * (f0 + j)], r1 = rec[3 * (f0 + j) + 1], r2 = rec[3 * (f0 + j) + 2];
+                if (!(r2.y >= 0.0f)) continue;
+                const MeshTri t = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x};
+                consider(t, __float_as_int(r2.z));
+            }
+        };
+        CellBlock old = {0, -1, 0, -1, 0, -1};
+        for (int ring = 1; ring <= res; ++ring) {
+            const CellBlock now = {max(cx - ring, 0), min(cx + ring, res - 1), max(cy - ring, 0), min(cy + ring, res - 1),
+                                   max(cz - ring, 0), min(cz + ring, res - 1)};
+            cross_visit_shell(off, res, old, now, visit);
+            old = now;
+            // squared distance from the query to every unvisited CENTROID (nearest_query_kernel's bound)
+            const float b2 = cross_unvisited_b2(g, res, gap, now.x0, now.x1, now.y0, now.y1, now.z0, now.z1, qx, qx, qy, qy, qz, qz);
+            if (b2 == __builtin_huge_valf() || best < mesh_floor(b2, rgrid, edge_max, kgrid)) break;
+            if (!(qx == qx && qy == qy && qz == qz)) break;   // a NaN query compares with nothing: no ring changes that
+        }
+    }
+    // (a d2 that is not below +inf is no answer: a NaN query's minimum stays at the +inf it started from)
+    const bool found = bid != 0x7fffffff && best < __builtin_huge_valf();
+    d2_out[i] = found ? best : 0.0f;
+    idx_out[i] = found ? (int64_t)bid - f0 : -1;
+}
+
+// one wavefront per face; 256-thread workgroups hold four faces
+__global__ __launch_bounds__(256) void face_point_query_kernel(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ faces,
+                                                               const int64_t *__restrict__ f_first, const int64_t *__restrict__ f_num,
+                                                               int64_t F, const int64_t *__restrict__ p_first,
+                                                               const int64_t *__restrict__ p_num, int64_t P, int N,
+                                                               const KnnGrid *__restrict__ grids, size_t stride,
+                                                               const uint32_t *__restrict__ offsets, const float4 *__restrict__ sorted,
+                                                               float *__restrict__ d2_out, int64_t *__restrict__ idx_out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t f = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (f >= F) return;
+    const int m = find_cloud(f, f_first, f_num, N);
+    MeshTri t;
+    int64_t p0 = 0, pn = 0;
+    if (m >= 0) { p0 = p_first[m]; pn = p_num[m]; }
+    // (wave-uniform) a slot of no mesh, an empty or misplaced cloud, an absent face
+    if (m < 0 || pn <= 0 || p0 < 0 || p0 + pn > P || !mesh_load_face(f, faces, verts, V, t)) {   // (0 <= f < F)
+        if (lane == 0) { d2_out[f] = 0.0f; idx_out[f] = -1; }
+        return;
+    }
+    const KnnGrid g = grids[m];
+    const uint32_t *off = offsets + (size_t)m * stride;
+    const int res = g.res;
+    const float lox = fminf(fminf(t.ax, t.bx), t.cx), hix = fmaxf(fmaxf(t.ax, t.bx), t.cx);
+    const float loy = fminf(fminf(t.ay, t.by), t.cy), hiy = fmaxf(fmaxf(t.ay, t.by), t.cy);
+    const float loz = fminf(fminf(t.az, t.bz), t.cz), hiz = fmaxf(fmaxf(t.az, t.bz), t.cz);
+    const int cx0 = nearest_start_cell(lox, g.minx, g.inv_cell, res), cx1 = nearest_start_cell(hix, g.minx, g.inv_cell, res);
+    const int cy0 = nearest_start_cell(loy, g.miny, g.inv_cell, res), cy1 = nearest_start_cell(hiy, g.miny, g.inv_cell, res);
+    const int cz0 = nearest_start_cell(loz, g.minz, g.inv_cell, res), cz1 = nearest_start_cell(hiz, g.minz, g.inv_cell, res);
+    const CrossGap gap = cross_gap(g, (float)res * g.cell, lox, hix, loy, hiy, loz, hiz);
+    const float ddx = hix - lox, ddy = hiy - loy, ddz = hiz - loz;
+    const float edge_max = sqrtf((ddx * ddx + ddy * ddy) + ddz * ddz) * 1.000001f;
+    const float kappa = mesh_kappa(t);
+    float best = __builtin_huge_valf();
+    int bid = 0x7fffffff;
+    auto visit = [&](uint32_t s, uint32_t e) __attribute__((always_inline)) {
+        for (uint32_t j = s + (uint32_t)lane; j < e; j += 64u) {
+            const float4 q = sorted[p0 + j];
+            const float d2 = mesh_d2f(q.x, q.y, q.z, t);
+            const int id = __float_as_int(q.w);
+            const bool lt = (d2 < best) | ((d2 == best) & (id < bid));
+            best = lt ? d2 : best;
+            bid = lt ? id : bid;
+        }
+    };
+    CellBlock old = {0, -1, 0, -1, 0, -1};   // the block already visited (empty before ring 0)
+    for (int ring = 0; ring <= res; ++ring) {
+        const CellBlock now = {max(cx0 - ring, 0), min(cx1 + ring, res - 1), max(cy0 - ring, 0), min(cy1 + ring, res - 1),
+                               max(cz0 - ring, 0), min(cz1 + ring, res - 1)};
+        cross_visit_shell(off, res, old, now, visit);
+        old = now;
+        const float b2 = cross_unvisited_b2(g, res, gap, now.x0, now.x1, now.y0, now.y1, now.z0, now.z1, lox, hix, loy, hiy, loz, hiz);
+        if (b2 == __builtin_huge_valf()) break;   // (wave-uniform: every operand is)
+        float wbest = best;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) wbest = fminf(wbest, __shfl_xor(wbest, o));
+        if (wbest < mesh_floor(b2, 0.0f, edge_max, kappa)) break;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bid, o);
+        const bool lt = (ob < best) | ((ob == best) & (oi < bid));
+        best = lt ? ob : best;
+        bid = lt ? oi : bid;
+    }
+    if (lane == 0) {
+        const bool found = bid != 0x7fffffff && best < __builtin_huge_valf();   // (as in point_face_query_kernel)
+        d2_out[f] = found ? best : 0.0f;
+        idx_out[f] = found ? (int64_t)bid - p0 : -1;
+    }
+}
+
+// ---- backward: d2 = |q - c*|^2 with c* = wa A + wb B + wc C held to its face; r = q - c* in double from the fp32 inputs
+struct MeshPair { double rx, ry, rz, wa, wb, wc; };
+// REQUIRES 0 <= i < P and 0 <= f < F.  false: the face is absent (contributes nothing)
+__device__ __forceinline__ bool mesh_pair(int64_t i, int64_t f, const float *__restrict__ pts, const float *__restrict__ verts, int64_t V,
+                                          const int64_t *__restrict__ faces, MeshPair &o)
+{
+    MeshTri t;
+    if (!mesh_load_face(f, faces, verts, V, t)) return false;
+    const double qx = pts[3 * i], qy = pts[3 * i + 1], qz = pts[3 * i + 2];
+    mesh_d2<double, true>(qx, qy, qz, t.ax, t.ay, t.az, t.bx, t.by, t.bz, t.cx, t.cy, t.cz, o.wa, o.wb, o.wc);
+    o.rx = qx - ((o.wa * t.ax + o.wb * t.bx) + o.wc * t.cx);
+    o.ry = qy - ((o.wa * t.ay + o.wb * t.by) + o.wc * t.cy);
+    o.rz = qz - ((o.wa * t.az + o.wb * t.bz) + o.wc * t.cz);
+    return true;
+}
+
+struct MeshLists {
+    const int64_t *p_first, *p_num, *f_first, *f_num;
+    int N;
+    int64_t P, F, V;
+    const int64_t *idx_pf, *idx_fp;   // (P,) mesh-local face of every point, (F,) cloud-local point of every face
+};
+#define MESH_NO_KEY 0x7fffffffffffffffll
+// the pair a point names: its packed face, or -1
+__device__ __forceinline__ int64_t mesh_face_of_point(const MeshLists &l, int64_t i)
+{
+    if ((uint64_t)i >= (uint64_t)l.P) return -1;
+    const int n = find_cloud(i, l.p_first, l.p_num, l.N);
+    const int64_t t = l.idx_pf[i];
+    if (n < 0 || t < 0) return -1;
+    const int64_t f = l.f_first[n] + t;
+    return (uint64_t)f < (uint64_t)l.F ? f : -1;
+}
+// the pair a face names: its packed point, or -1
+__device__ __forceinline__ int64_t mesh_point_of_face(const MeshLists &l, int64_t f)
+{
+    if ((uint64_t)f >= (uint64_t)l.F) return -1;
+    const int m = find_cloud(f, l.f_first, l.f_num, l.N);
+    const int64_t t = l.idx_fp[f];
+    if (m < 0 || t < 0) return -1;
+    const int64_t i = l.p_first[m] + t;
+    return (uint64_t)i < (uint64_t)l.P ? i : -1;
+}
+// entry e = 3 pair + corner of the vertices' contributor list; pairs [0, P) are the points' (i, face of i), pairs
+// [P, P + F) the faces' (point of f, f).  -> the packed vertex the entry adds to (MESH_NO_KEY: none), its pair (i, f)
+__device__ __forceinline__ int64_t mesh_vertex_entry(const MeshLists &l, const int64_t *__restrict__ faces, int64_t e, int64_t &i, int64_t &f)
+{
+    if ((uint64_t)e >= (uint64_t)(3 * (l.P + l.F))) return MESH_NO_KEY;
+    const int64_t pair = e / 3;
+    const int k = (int)(e - 3 * pair);
+    if (pair < l.P) { i = pair; f = mesh_face_of_point(l, pair); }
+    else { f = pair - l.P; i = mesh_point_of_face(l, f); }
+    if (i < 0 || f < 0) return MESH_NO_KEY;
+    const int64_t v = faces[3 * f + k];   // (0 <= f < F: both helpers return -1 otherwise)
+    return (uint64_t)v < (uint64_t)l.V ? v : MESH_NO_KEY;
+}
+
+// one thread per output row: threads [0, P) write grad_points, threads [P, P + V) grad_verts (each when given).  Its
+// contributors are one segment of a list sorted in the Python layer (stable sort of int64 keys): found by binary search,
+// added front to back in double, rounded once.
+__global__ __launch_bounds__(256) void mesh_backward_kernel(const float *__restrict__ pts, const float *__restrict__ verts,
+                                                            const int64_t *__restrict__ faces, const MeshLists l,
+                                                            const int64_t *__restrict__ order_f /* (F,) */,
+                                                            const int64_t *__restrict__ order_v /* (3 (P + F),) */,
+                                                            const float *__restrict__ g_p, const float *__restrict__ g_f,
+                                                            float *__restrict__ grad_points, float *__restrict__ grad_verts)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    MeshPair pr;
+    if (t < l.P) {
+        if (!grad_points) return;
+        const int64_t i = t;
+        const int64_t fown = mesh_face_of_point(l, i);
+        if (fown >= 0 && mesh_pair(i, fown, pts, verts, l.V, faces, pr)) {
+            const double w = 2.0 * (double)g_p[i];
+            s0 = w * pr.rx; s1 = w * pr.ry; s2 = w * pr.rz;
+        }
+        int64_t lo = 0, hi = l.F;   // first k whose face names a point >= i (no point: behind every real one)
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            const int64_t tgt = mesh_point_of_face(l, order_f[mid]);
+            if ((tgt < 0 ? MESH_NO_KEY : tgt) < i) lo = mid + 1;
+            else hi = mid;
+        }
+        for (int64_t k = lo; k < l.F; ++k) {
+            const int64_t f = order_f[k];
+            if (mesh_point_of_face(l, f) != i) break;
+            if (!mesh_pair(i, f, pts, verts, l.V, faces, pr)) continue;
+            const double w = 2.0 * (double)g_f[f];
+            s0 += w * pr.rx; s1 += w * pr.ry; s2 += w * pr.rz;
+        }
+        grad_points[3 * i] = (float)s0; grad_points[3 * i + 1] = (float)s1; grad_points[3 * i + 2] = (float)s2;
+    } else if (t < l.P + l.V) {
+        if (!grad_verts) return;
+        const int64_t v = t - l.P, E = 3 * (l.P + l.F);
+        int64_t i = -1, f = -1;
+        int64_t lo = 0, hi = E;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (mesh_vertex_entry(l, faces, order_v[mid], i, f) < v) lo = mid + 1;
+            else hi = mid;
+        }
+        for (int64_t k = lo; k < E; ++k) {
+            const int64_t e = order_v[k];
+            if (mesh_vertex_entry(l, faces, e, i, f) != v) break;
+            if (!mesh_pair(i, f, pts, verts, l.V, faces, pr)) continue;
+            const int corner = (int)(e % 3);
+            const double wk = corner == 0 ? pr.wa : (corner == 1 ? pr.wb : pr.wc);
+            const double w = -2.0 * (double)(e / 3 < l.P ? g_p[i] : g_f[f]) * wk;
+            s0 += w * pr.rx; s1 += w * pr.ry; s2 += w * pr.rz;
+        }
+        grad_verts[3 * v] = (float)s0; grad_verts[3 * v + 1] = (float)s1; grad_verts[3 * v + 2] = (float)s2;
+    }
+}
+
+}  // namespace dss
+
+// The regions behind the grid's own workspace (the grid is built over F centroids)
+struct MeshWorkspace {
+    float *cent;      // (F,3) centroids
+    float *rf;        // (F) radii
+    float4 *rec;      // (3 F) the faces in cell order
+    int *large;       // (F) large lists, mesh n's at f_first[n]
+    int *per_mesh;    // (N,3) bits of R_grid, length of the large list, bits of K_grid
+    float *kap;       // (F) kappa of every face
+    size_t bytes;
+};
+static MeshWorkspace carve_mesh(void *ws, int N, int64_t F)
+{
+    MeshWorkspace m = {};
+    const size_t n = N > 0 ? N : 1, f = F > 0 ? F : 1;
+    Bump b = {reinterpret_cast<char *>(ws), align_up(carve_knn(nullptr, N, F).bytes, 256)};
+    m.cent = b.take<float>(3 * f);
+    m.rf = b.take<float>(f);
+    m.rec = b.take<float4>(3 * f);
+    m.large = b.take<int>(f);
+    m.per_mesh = b.take<int>(3 * n);
+    m.kap = b.take<float>(f);
+    m.bytes = b.used;
+    return m;
+}
+
+extern "C" size_t dss_point_face_workspace(int N, int64_t F) { return carve_mesh(nullptr, N, F).bytes; }
+
+static int mesh_check_sizes(const char *who, int N, int64_t P, int64_t V, int64_t F)
+{
+    if (N <= 0 || P < 0 || V < 0 || F < 0 || P > 0x7fffffffll || F > 0x7fffffffll) {
+        set_error("%s: bad sizes N=%d P=%lld V=%lld F=%lld (P, F below 2^31)", who, N, (long long)P, (long long)V, (long long)F);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    return DSS_OK;
+}
+
+extern "C" int dss_point_face_distance(const float *points, const int64_t *p_first, const int64_t *p_num, int64_t P,
+                                       const float *verts, int64_t V, const int64_t *faces, const int64_t *f_first,
+                                       const int64_t *f_num, int64_t F, int N, float *d2, int64_t *idx, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    const char *who = "dss_point_face_distance";
+    if (int rc = mesh_check_sizes(who, N, P, V, F)) return rc;
+    if (P == 0) return DSS_OK;
+    if (!points || !p_first || !p_num || !f_first || !f_num || !d2 || !idx || (F > 0 && !faces) || (V > 0 && !verts)) {
+        set_error("%s: NULL tensor pointer", who);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (!workspace || workspace_bytes < dss_point_face_workspace(N, F)) {
+        set_error("%s: workspace too small", who);
+        return DSS_ERR_WORKSPACE;
+    }
+    const MeshWorkspace m = carve_mesh(workspace, N, F);
+    // the grid of the centroids, by the self query's build (the plan only matters to the queries above: none is launched)
+    const KnnCall c = {who, m.cent, f_first, f_num, N, F, 1, nullptr, nullptr, -1.0f, as_stream(stream), carve_knn(workspace, N, F),
+                       plan_query(F, 1, false)};
+    if (hipMemsetAsync(m.per_mesh, 0, (size_t)N * 12, c.st) != hipSuccess) return check_launch("mesh memset");
+    if (F > 0) {
+        const unsigned fb = (unsigned)((F + 255) / 256);
+        const int q = option(DSS_OPT_MESH_LARGE);
+        hipLaunchKernelGGL(mesh_prep_kernel, dim3(fb), dim3(256), 0, c.st, verts, V, faces, f_first, f_num, N, F, m.cent, m.rf, m.kap);
+        if (int rc = build_grid(c, KnnView())) return rc;
+        hipLaunchKernelGGL(mesh_classify_kernel, dim3(fb), dim3(256), 0, c.st, f_first, f_num, N, F, c.w.grids, (float)(q > 0 ? q : MESH_LARGE_QUARTERS),
+                           m.rf, m.kap, m.per_mesh, m.large);
+        hipLaunchKernelGGL(mesh_gather_kernel, dim3(fb), dim3(256), 0, c.st, verts, V, faces, f_first, f_num, N, F, c.w.sorted, m.rf, m.rec);
+    }
+    const unsigned block = P <= 131072 ? 64u : 256u;
+    hipLaunchKernelGGL(point_face_query_kernel, dim3((unsigned)((P + block - 1) / block)), dim3(block), 0, c.st, points, p_first, p_num, P,
+                       verts, V, faces, f_first, f_num, F, N, c.w.grids, c.w.stride, c.w.offsets, c.w.sorted, m.rec, m.per_mesh, m.large,
+                       d2, idx);
+    return check_launch(who);
+}
+
+extern "C" int dss_face_point_distance(const float *points, const int64_t *p_first, const int64_t *p_num, int64_t P,
+                                       const float *verts, int64_t V, const int64_t *faces, const int64_t *f_first,
+                                       const int64_t *f_num, int64_t F, int N, float *d2, int64_t *idx, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    const char *who = "dss_face_point_distance";
+    if (int rc = mesh_check_sizes(who, N, P, V, F)) return rc;
+    if (F == 0) return DSS_OK;
+    if (!p_first || !p_num || !f_first || !f_num || !faces || !d2 || !idx || (P > 0 && !points) || (V > 0 && !verts)) {
+        set_error("%s: NULL tensor pointer", who);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (!workspace || workspace_bytes < dss_nearest_workspace(N, P)) {
+        set_error("%s: workspace too small", who);
+        return DSS_ERR_WORKSPACE;
+    }
+    const KnnCall c = {who, points, p_first, p_num, N, P, 1, nullptr, nullptr, -1.0f, as_stream(stream), carve_knn(workspace, N, P),
+                       plan_query(P, 1, false)};
+    if (P > 0)
+        if (int rc = build_grid(c, KnnView())) return rc;
+    hipLaunchKernelGGL(face_point_query_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, c.st, verts, V, faces, f_first, f_num, F,
+                       p_first, p_num, P, N, c.w.grids, c.w.stride, c.w.offsets, c.w.sorted, d2, idx);
+    return check_launch(who);
+}
+
+extern "C" int dss_mesh_distance_backward(const float *points, const int64_t *p_first, const int64_t *p_num, int64_t P,
+                                          const float *verts, int64_t V, const int64_t *faces, const int64_t *f_first,
+                                          const int64_t *f_num, int64_t F, int N, const int64_t *idx_pf, const int64_t *idx_fp,
+                                          const int64_t *order_f, const int64_t *order_v, const float *g_p, const float *g_f,
+                                          float *grad_points, float *grad_verts, void *stream)
+{
+    const char *who = "dss_mesh_distance_backward";
+    if (int rc = mesh_check_sizes(who, N, P, V, F)) return rc;
+    if ((!grad_points || P == 0) && (!grad_verts || V == 0)) return DSS_OK;
+    if (!p_first || !p_num || !f_first || !f_num || (P > 0 && (!points || !idx_pf || !g_p)) || (F > 0 && (!faces || !idx_fp || !g_f)) ||
+        (V > 0 && !verts) || (grad_points && F > 0 && !order_f) || (grad_verts && P + F > 0 && !order_v)) {
+        set_error("%s: NULL tensor pointer", who);
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    const int64_t blocks = (P + V + 255) / 256;
+    if (blocks > 0x7fffffffll) { set_error("%s: too many rows", who); return DSS_ERR_UNSUPPORTED; }
+    const MeshLists l = {p_first, p_num, f_first, f_num, N, P, F, V, idx_pf, idx_fp};
+    hipLaunchKernelGGL(mesh_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), points, verts, faces, l, order_f,
+                       order_v, g_p, g_f, grad_points, grad_verts);
     return check_launch(who);
 }

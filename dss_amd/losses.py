@@ -311,6 +311,100 @@ class _Chamfer(autograd.Function):
         return (sx.unpack_grad(grad_x) if want_x else None, sy.unpack_grad(grad_y) if want_y else None, None, None, None, None, None)
 
 
+class _MeshSide:
+    """The meshes of `point_mesh_face_distance` as packed arrays: ``verts`` (V,3) is the tensor autograd sees, ``faces``
+    (F,3) holds packed vertex ids, ``first`` / ``num`` (N,) the faces of every mesh."""
+
+    def __init__(self, meshes):
+        if isinstance(meshes, (tuple, list)) and len(meshes) == 2 and isinstance(meshes[0], (tuple, list)):
+            verts_list, faces_list = meshes
+            if len(verts_list) != len(faces_list) or len(verts_list) == 0:
+                raise ValueError("point_mesh_face_distance: (verts, faces) must be two lists of equal, non-zero length")
+            self.sizes = [int(f.shape[0]) for f in faces_list]
+            self.verts = torch.cat(list(verts_list), 0)
+            starts, run = [], 0
+            for v in verts_list:
+                starts.append(run)
+                run += int(v.shape[0])
+            self.faces = torch.cat([f.to(torch.int64) + s for f, s in zip(faces_list, starts)], 0)
+        elif hasattr(meshes, "verts_packed") and hasattr(meshes, "faces_packed"):
+            self.verts, self.faces = meshes.verts_packed(), meshes.faces_packed().to(torch.int64)
+            if hasattr(meshes, "faces_list"):   # host-side sizes: no device synchronisation
+                self.sizes = [int(f.shape[0]) for f in meshes.faces_list()]
+            else:                               # (an object without host-side sizes costs one host read per call)
+                self.sizes = [int(v) for v in meshes.num_faces_per_mesh().tolist()]
+        else:
+            raise ValueError("point_mesh_face_distance: meshes must offer pytorch3d's packed accessors or be a (verts, faces) "
+                             "pair of lists")
+        if len(self.sizes) == 0 or any(s <= 0 for s in self.sizes) or self.verts.shape[0] == 0:
+            raise ValueError("point_mesh_face_distance: an empty mesh (faces %s, %d vertices): its mean distance is undefined"
+                             % (self.sizes, self.verts.shape[0]))
+        dev = self.verts.device
+        if hasattr(meshes, "mesh_to_faces_packed_first_idx"):
+            self.first, self.num = meshes.mesh_to_faces_packed_first_idx().to(torch.int64), meshes.num_faces_per_mesh().to(torch.int64)
+        else:
+            first, run = [], 0
+            for s in self.sizes:
+                first.append(run)
+                run += s
+            self.first = torch.tensor(first, dtype=torch.int64, device=dev)
+            self.num = torch.tensor(self.sizes, dtype=torch.int64, device=dev)
+        self.F = sum(self.sizes)
+
+
+class _PointMeshFace(autograd.Function):
+    """Both searches and the reductions as ONE node; backward = dss_mesh_distance_backward."""
+
+    @staticmethod
+    def forward(ctx, p_src, verts, sp, sm):
+        pts, v = sp.pack(p_src.detach()), verts.detach().contiguous()
+        d2p, idx_pf = ops.point_face_distance(pts, sp.first, sp.num, v, sm.faces, sm.first, sm.num)
+        d2f, idx_fp = ops.face_point_distance(pts, sp.first, sp.num, v, sm.faces, sm.first, sm.num)
+        N = len(sp.sizes)
+        kp = 1.0 / (sp.num.to(pts.dtype) * N)     # d loss / d (squared distance of a point of cloud n)
+        kf = 1.0 / (sm.num.to(pts.dtype) * N)
+        cp = sp.per_point(kp)
+        cf = torch.repeat_interleave(kf, sm.num, output_size=sm.F)
+        loss = (d2p * cp).sum() + (d2f * cf).sum()
+        ctx.save_for_backward(pts, v, idx_pf, idx_fp, cp, cf)
+        ctx.sides = (sp, sm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        pts, v, idx_pf, idx_fp, cp, cf = ctx.saved_tensors
+        sp, sm = ctx.sides
+        want_p, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gp, gv = ops.mesh_distance_backward(pts, sp.first, sp.num, v, sm.faces, sm.first, sm.num, idx_pf, idx_fp,
+                                            grad_loss * cp, grad_loss * cf, want_p, want_v)
+        return (sp.unpack_grad(gp) if want_p else None, gv if want_v else None, None, None)
+
+
+def point_mesh_face_distance(meshes, pcls, min_triangle_area=None):
+    """``pytorch3d.loss.point_mesh_face_distance`` on the HIP path: for cloud n against mesh n,
+    ``sum_p d2_p / (|cloud(p)| N) + sum_f d2_f / (|mesh(f)| N)`` with d2_p the squared distance of a point to its nearest
+    face (``dss_point_face_distance``) and d2_f of a face to its nearest point (``dss_face_point_distance``), under the one
+    distance of include/dss_hip.h.  One autograd node, differentiable w.r.t. the points and the vertices (face assignment
+    held constant, deterministic).
+
+    ``meshes``: any object with pytorch3d's ``verts_packed() / faces_packed() / mesh_to_faces_packed_first_idx() /
+    num_faces_per_mesh()`` (``faces_packed()`` already holds packed vertex ids, so the two vertex accessors
+    ``mesh_to_verts_packed_first_idx() / num_verts_per_mesh()`` are not read; ``faces_list()``, when offered, spares a host
+    read of the sizes), or a ``(verts, faces)`` pair of lists (faces then hold mesh-local vertex ids).  ``pcls``: a `dss_amd.cloud.PointClouds3D` or a padded (N,P,3) tensor, as in
+    `chamfer_distance`.  An empty cloud or mesh raises ValueError.  ``min_triangle_area`` is accepted and ignored: the
+    distance treats a degenerate triangle as the union of its edges and needs no threshold (pytorch3d's absolute 5e-3
+    turns small valid triangles into edge sets)."""
+    del min_triangle_area
+    sm = _MeshSide(meshes)
+    try:
+        sp = _ChamferSide(pcls, None, None, "pcls")
+    except ValueError as e:
+        raise ValueError(str(e).replace("chamfer_distance", "point_mesh_face_distance"))
+    if len(sp.sizes) != len(sm.sizes):
+        raise ValueError("point_mesh_face_distance: %d clouds against %d meshes" % (len(sp.sizes), len(sm.sizes)))
+    return _PointMeshFace.apply(sp.src, sm.verts, sp, sm)
+
+
 def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
                      batch_reduction="mean", point_reduction: str = "mean"):
     """``pytorch3d.loss.chamfer_distance`` -- the 3-D metric of `Trainer.evaluate_3d` (trainer.py:144-171,

@@ -1,0 +1,109 @@
+"""Operators between packed clouds and packed triangle meshes: the nearest face of mesh n for every point of cloud n
+(``dss_point_face_distance``), the nearest point of cloud n for every face of mesh n (``dss_face_point_distance``) and the
+gradient of both (``dss_mesh_distance_backward``) -- the p2f columns of the reference's evaluation row
+(scripts/evaluatePointClouds.py:52,103-132) and ``pytorch3d.loss.point_mesh_face_distance``.  The distance is defined once
+in include/dss_hip.h.  Re-exported by `dss_amd.ops`; written like `cross_cloud.py` and entering the library the same way,
+through `_lib.call`: tensors checked by `_lib.require_gpu`, no CPU fallback.
+"""
+import torch
+
+from . import _lib
+from .cross_cloud import packed_cloud_ids
+
+_f32, _i64 = torch.float32, torch.int64
+_on_device = _lib.on_device
+_NO_KEY = torch.iinfo(_i64).max
+
+
+def _gpu(dtype, **tensors):
+    return [_lib.require_gpu(t, name, dtype) for name, t in tensors.items()]
+
+
+def _mesh_inputs(points, p_first, p_num, verts, faces, f_first, f_num):
+    """What the three entries share: the seven checked tensors, N, P, V, F and the device."""
+    points, verts = _gpu(_f32, points=points, verts=verts)
+    pf, pn, faces, ff, fn = _gpu(_i64, p_first=p_first, p_num=p_num, faces=faces, f_first=f_first, f_num=f_num)
+    N = pf.shape[0]
+    if (points.dim() != 2 or verts.dim() != 2 or faces.dim() != 2 or points.shape[1] != 3 or verts.shape[1] != 3 or faces.shape[1] != 3
+            or pf.dim() != 1 or pn.shape != pf.shape or ff.shape != pf.shape or fn.shape != pf.shape
+            or verts.device != points.device or faces.device != points.device):
+        raise RuntimeError("points (P,3), verts (V,3) float32 and faces (F,3) int64 on one device, with as many meshes (%s) as "
+                           "clouds (%d)" % (tuple(ff.shape), N))
+    return points, pf, pn, verts, faces, ff, fn, N, points.shape[0], verts.shape[0], faces.shape[0], points.device
+
+
+def point_face_distance(points, p_first, p_num, verts, faces, f_first, f_num):
+    """Nearest face of mesh n for every point of cloud n -> (d2 (P,) squared distance, idx (P,) int64 mesh-local face id;
+    ties to the smaller id).  ``faces`` holds PACKED vertex ids.  A point of no cloud, a point with a NaN position and a
+    point whose mesh has no usable face get (0, -1); a face with a vertex id outside [0, V) or a non-finite vertex is
+    absent.  Exact grid search over the centroids in HIP (``dss_point_face_distance``)."""
+    points, pf, pn, verts, faces, ff, fn, N, P, V, F, dev = _mesh_inputs(points, p_first, p_num, verts, faces, f_first, f_num)
+    with _on_device(dev):
+        d2 = torch.empty((P,), dtype=_f32, device=dev)
+        idx = torch.empty((P,), dtype=_i64, device=dev)
+        ws = _lib.workspace(dev, _lib.load().dss_point_face_workspace(N, F))
+        _lib.call("dss_point_face_distance", dev, points, pf, pn, P, verts, V, faces, ff, fn, F, N, d2, idx, ws, ws.numel())
+    return d2, idx
+
+
+def face_point_distance(points, p_first, p_num, verts, faces, f_first, f_num):
+    """Nearest point of cloud n for every face of mesh n, under the same distance -> (d2 (F,), idx (F,) int64 cloud-local
+    point id; ties to the smaller id).  A face of no mesh, an absent face and a face whose cloud has no usable point get
+    (0, -1).  One wavefront per face over the cloud's point grid (``dss_face_point_distance``)."""
+    points, pf, pn, verts, faces, ff, fn, N, P, V, F, dev = _mesh_inputs(points, p_first, p_num, verts, faces, f_first, f_num)
+    with _on_device(dev):
+        d2 = torch.empty((F,), dtype=_f32, device=dev)
+        idx = torch.empty((F,), dtype=_i64, device=dev)
+        ws = _lib.workspace(dev, _lib.load().dss_nearest_workspace(N, P))
+        _lib.call("dss_face_point_distance", dev, points, pf, pn, P, verts, V, faces, ff, fn, F, N, d2, idx, ws, ws.numel())
+    return d2, idx
+
+
+def _pair_targets(idx, own_first, own_num, target_first, n_target):
+    """Packed id on the other side that every slot of one side names -> (own,) int64, -1 where there is none."""
+    cloud = packed_cloud_ids(own_first, own_num, idx.shape[0])
+    tgt = target_first[cloud.clamp(min=0)] + idx
+    return torch.where((cloud >= 0) & (idx >= 0) & (tgt >= 0) & (tgt < n_target), tgt, torch.full_like(tgt, -1))
+
+
+def mesh_distance_orders(faces, V, idx_pf, idx_fp, p_first, p_num, f_first, f_num, want_points=True, want_verts=True):
+    """The two contributor lists of ``dss_mesh_distance_backward`` (stable `torch.sort` of int64 keys, as
+    `cross_cloud.chamfer_order`): ``order_f`` (F,) = the packed face ids by (packed id of their point, own id);
+    ``order_v`` (3 (P + F),) = the entries 3 pair + corner by (packed id of the vertex at that corner, entry)."""
+    P, F = idx_pf.shape[0], idx_fp.shape[0]
+    point_of_face = _pair_targets(idx_fp, f_first, f_num, p_first, P)
+    order_f = order_v = None
+    if want_points:
+        order_f = torch.sort(torch.where(point_of_face >= 0, point_of_face, torch.full_like(point_of_face, _NO_KEY)),
+                             stable=True).indices
+    if want_verts:
+        face_of_point = _pair_targets(idx_pf, p_first, p_num, f_first, F)
+        pair_face = torch.cat([face_of_point, torch.where(point_of_face >= 0, torch.arange(F, dtype=_i64, device=faces.device),
+                                                          torch.full_like(point_of_face, -1))])
+        if F > 0:
+            vid = faces[pair_face.clamp(min=0)]                     # (P + F, 3); rows of pairs that do not exist are masked below
+        else:
+            vid = torch.full((P, 3), -1, dtype=_i64, device=faces.device)
+        key = torch.where((pair_face >= 0)[:, None] & (vid >= 0) & (vid < V), vid, torch.full_like(vid, _NO_KEY))
+        order_v = torch.sort(key.reshape(-1), stable=True).indices
+    return order_f, order_v
+
+
+def mesh_distance_backward(points, p_first, p_num, verts, faces, f_first, f_num, idx_pf, idx_fp, g_p, g_f,
+                           want_points: bool = True, want_verts: bool = True):
+    """Gradient of the two searches (``dss_mesh_distance_backward``) with their index lists (`point_face_distance`:
+    ``idx_pf``, `face_point_distance`: ``idx_fp``) held constant, ``g_p`` (P,) / ``g_f`` (F,) = d loss / d squared
+    distance -> (grad_points (P,3) or None, grad_verts (V,3) or None), fully written, bitwise reproducible (no atomics:
+    see `mesh_distance_orders`)."""
+    points, pf, pn, verts, faces, ff, fn, N, P, V, F, dev = _mesh_inputs(points, p_first, p_num, verts, faces, f_first, f_num)
+    idx_pf, idx_fp = _gpu(_i64, idx_pf=idx_pf, idx_fp=idx_fp)
+    g_p, g_f = _gpu(_f32, g_p=g_p, g_f=g_f)
+    if idx_pf.shape != (P,) or g_p.shape != (P,) or idx_fp.shape != (F,) or g_f.shape != (F,):
+        raise RuntimeError("mesh_distance_backward: idx_pf, g_p (P,) and idx_fp, g_f (F,) with P=%d F=%d" % (P, F))
+    with _on_device(dev):
+        order_f, order_v = mesh_distance_orders(faces, V, idx_pf, idx_fp, pf, pn, ff, fn, want_points, want_verts)
+        grad_points = torch.empty((P, 3), dtype=_f32, device=dev) if want_points else None
+        grad_verts = torch.empty((V, 3), dtype=_f32, device=dev) if want_verts else None
+        _lib.call("dss_mesh_distance_backward", dev, points, pf, pn, P, verts, V, faces, ff, fn, F, N, idx_pf, idx_fp, order_f,
+                  order_v, g_p, g_f, grad_points, grad_verts)
+    return grad_points, grad_verts

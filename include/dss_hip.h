@@ -86,6 +86,9 @@ DSS_API const char *dss_last_error(void);
  *                             [N + 8, automatic].  Exists so that a test can reach every dealing case of the gather (full
  *                             rounds, a claimed last round) with a few thousand points, and for A/B measurements of grid
  *                             sizes.  Results do not depend on it.
+ *   DSS_OPT_MESH_LARGE      dss_point_face_distance: triangles whose radius exceeds value / 4 grid cells are tested by
+ *                             every query of their mesh instead of through the grid; 0 (default) = 8 (two cells), up to
+ *                             4096.  For A/B measurements (tools/mesh_distance_timing.py).  Results do not depend on it.
  * Returns DSS_ERR_INVALID_ARGUMENT for an unknown option or value. */
 #define DSS_OPT_LEAN_WORKSPACE 0
 #define DSS_OPT_BACKWARD_TPW 1
@@ -93,7 +96,8 @@ DSS_API const char *dss_last_error(void);
 #define DSS_OPT_BACKWARD_FUSED 3
 #define DSS_OPT_KNN_QUERY 4
 #define DSS_OPT_BACKWARD_GRID 5
-#define DSS_OPT_COUNT 6
+#define DSS_OPT_MESH_LARGE 6
+#define DSS_OPT_COUNT 7
 DSS_API int dss_band_rows(int row0, int row1, int row_cycle); /* rows of a band tensor (see `row_cycle` above) */
 DSS_API int dss_set_option(int option, int value);
 DSS_API int dss_get_option(int option);
@@ -578,6 +582,64 @@ DSS_API int dss_chamfer_backward(const float *x, const float *y,
                                  const int64_t *order_xy /* (Px,) */, const int64_t *order_yx /* (Py,) */,
                                  const float *gx /* (Px,) d loss / d d2_x */, const float *gy /* (Py,) */,
                                  float *grad_x /* (Px,3) */, float *grad_y /* (Py,3) */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Point-to-mesh distance: nearest face of mesh n for every point of cloud n, nearest point of cloud n for every face of
+ * mesh n, and the gradient of both -- the "p2f" columns of the reference's evaluation row
+ * (scripts/evaluatePointClouds.py:52,103-132, read there from files an outside tool wrote) and the surface term
+ * pytorch3d.loss.point_mesh_face_distance [third party, not vendored; parity is to the definition below].
+ * points (P,3) packed clouds with p_first / p_num (N,); verts (V,3); faces (F,3) int64 PACKED vertex ids, packed meshes
+ * with f_first / f_num (N,).  P, F < 2^31.
+ * The distance of a query q and a triangle A B C, fp32 without contraction, correctly rounded division,
+ * dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z:
+ *   seg(q, P, R): p0 = the lexicographically smaller endpoint (x, y, z by value), e = p1 - p0, w = q - p0, ee = dot(e, e),
+ *       we = dot(w, e); we <= 0 or ee == 0: r = w; else we >= ee: r = q - p1; else t = we / ee, r = w - t e; -> dot(r, r)
+ *   n = (B - A) x (C - A), nn = dot(n, n); for A->B, B->C, C->A: s = dot((R - P) x (q - P), n); inside = nn > 0 and every
+ *       s > 0; plane = (h h) / nn, h = dot(q - A, n)
+ *   d2 = min under `<` (a NaN never wins) of seg(A,B), seg(B,C), seg(C,A), inside ? plane : +inf.
+ * A shared edge or vertex gives its faces the same bits; a degenerate triangle is the union of its edges; no threshold.
+ * A face with a vertex id outside [0, V), or with a non-finite vertex, is ABSENT: its vertices are not read through the
+ * bad id, it is never an answer, and it does not touch the search grid's box.
+ * dss_point_face_distance: d2 (P,), idx (P,) = the mesh-local face id, ties to the smaller id.  (0, -1) for a point of
+ * no cloud (its position is not read), a point with a NaN position, a point whose mesh has no usable face.  Exact:
+ * build_grid over the centroids, ring walk with the stop rule sqrt(best) <= bound - R_grid rounded the safe way (the
+ * allowance grows with the conditioning (longest edge)^2 / |n| of the mesh's triangles: the plane term of a sliver is that
+ * much less accurate), faces much larger than a cell or of conditioning above 256 on a per-mesh list every query tests
+ * (its length stays on the device).
+ * Workspace: dss_point_face_workspace(N, F), known on the host.
+ * dss_face_point_distance: d2 (F,), idx (F,) = the cloud-local id of the nearest point of cloud n, ties to the smaller
+ * id; (0, -1) for a face of no mesh, an absent face, a face whose cloud has no usable point.  One wavefront per face over
+ * the cloud's point grid.  Workspace: dss_nearest_workspace(N, P).
+ * dss_mesh_distance_backward: with both index lists held constant and c* = wa A + wb B + wc C the closest point of a
+ * pair (weights recomputed in double from the fp32 inputs by the rules above; the winner is the first minimum in the
+ * order AB, BC, CA, plane), d d2 / d q = 2 (q - c*), d d2 / d A = -2 wa (q - c*), likewise B, C.
+ *   grad_points[i] = g_p[i] d d2(i, face of i) / d q + sum over the faces f whose point is i of g_f[f] d d2(i, f) / d q
+ *   grad_verts[v]  = the sum over all P + F pairs and their corners that are vertex v
+ * g_p (P,), g_f (F,) = d loss / d d2 of the two searches.  No float atomics: order_f (F,) = the packed face ids sorted by
+ * (packed id of their point, own id), faces without a point last; order_v (3 (P + F),) = the entries e = 3 pair + corner
+ * (pairs [0, P): point i with its face, pairs [P, P + F): face f with its point) sorted by (packed id of the vertex at
+ * that corner, e), entries of pairs that do not exist or whose vertex id is outside [0, V) last.  One thread per output
+ * row finds its segment by binary search and adds it front to back in double, rounding once: a repeated call returns
+ * the same bits.  Both outputs are fully written; either may be NULL (then the order list only it needs may be NULL).
+ * ------------------------------------------------------------------------------------------- */
+DSS_API size_t dss_point_face_workspace(int N, int64_t F);
+DSS_API int dss_point_face_distance(const float *points /* (P,3) */, const int64_t *p_first, const int64_t *p_num, int64_t P,
+                                    const float *verts /* (V,3) */, int64_t V, const int64_t *faces /* (F,3) */,
+                                    const int64_t *f_first, const int64_t *f_num, int64_t F, int N,
+                                    float *d2 /* (P,) */, int64_t *idx /* (P,) mesh-local face id */,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+DSS_API int dss_face_point_distance(const float *points /* (P,3) */, const int64_t *p_first, const int64_t *p_num, int64_t P,
+                                    const float *verts /* (V,3) */, int64_t V, const int64_t *faces /* (F,3) */,
+                                    const int64_t *f_first, const int64_t *f_num, int64_t F, int N,
+                                    float *d2 /* (F,) */, int64_t *idx /* (F,) cloud-local point id */,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+DSS_API int dss_mesh_distance_backward(const float *points, const int64_t *p_first, const int64_t *p_num, int64_t P,
+                                       const float *verts, int64_t V, const int64_t *faces, const int64_t *f_first,
+                                       const int64_t *f_num, int64_t F, int N,
+                                       const int64_t *idx_pf /* (P,) */, const int64_t *idx_fp /* (F,) */,
+                                       const int64_t *order_f /* (F,) */, const int64_t *order_v /* (3 (P + F),) */,
+                                       const float *g_p /* (P,) d loss / d d2 */, const float *g_f /* (F,) */,
+                                       float *grad_points /* (P,3) */, float *grad_verts /* (V,3) */, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * One round of sparsity upsampling: `upsample` of DSS/core/cloud.py:555-632 inserts points where a neighbourhood is
