@@ -158,6 +158,7 @@ WS_ORDER_SAVE, WS_ORDER_REUSE = 0x10, 0x20   # include/dss_hip.h DSS_WS_ORDER_* 
 WS_BAND_OUTPUTS = 0x40   # DSS_WS_BAND_OUTPUTS: ellipse / scaler / cutoff only for the splats that meet the row band
 OPT_LEAN_WORKSPACE, OPT_BACKWARD_TPW, OPT_BACKWARD_ADDR64, OPT_BACKWARD_FUSED, OPT_KNN_QUERY, OPT_BACKWARD_GRID = 0, 1, 2, 3, 4, 5   # include/dss_hip.h DSS_OPT_*
 OPT_MESH_LARGE = 6
+OPT_FORWARD_FILL = 7   # 0 plain / 1 (default) write-through stores for the fine launch's empty-tile constants
 
 
 def set_option(option: int, value: int) -> int:

@@ -29,7 +29,9 @@ int check_launch(const char *what)
 
 // Process-wide option table of dss_set_option: the ONLY mutable process state besides the thread-local error string.
 // Relaxed atomics: an option is a tuning hint read once per call; callers change it between calls, not during one.
+// Every option starts at 0 but DSS_OPT_FORWARD_FILL, which is set to 1 (write-through, include/dss_hip.h) when the library loads.
 static std::atomic<int> g_opt[DSS_OPT_COUNT];
+static const bool g_opt_defaults_set = (g_opt[DSS_OPT_FORWARD_FILL].store(1, std::memory_order_relaxed), true);
 int option(int which) { return (which >= 0 && which < DSS_OPT_COUNT) ? g_opt[which].load(std::memory_order_relaxed) : 0; }
 
 // Per-device cache of the CU count and of the resident workgroups per CU of the kernels whose persistent grids are sized by
@@ -92,6 +94,10 @@ extern "C" int dss_set_option(int option, int value)
     }
     if (option == DSS_OPT_MESH_LARGE && (value < 0 || value > 4096)) {
         dss::set_error("dss_set_option: DSS_OPT_MESH_LARGE takes 0 (default) or 1 .. 4096 quarters of a cell");
+        return DSS_ERR_INVALID_ARGUMENT;
+    }
+    if (option == DSS_OPT_FORWARD_FILL && !(value == 0 || value == 1)) {
+        dss::set_error("dss_set_option: DSS_OPT_FORWARD_FILL takes 0 (plain stores) or 1 (write-through stores)");
         return DSS_ERR_INVALID_ARGUMENT;
     }
     dss::g_opt[option].store(value, std::memory_order_relaxed);

@@ -1120,6 +1120,28 @@ __device__ __forceinline__ void fill_tile_rows(const FineArgs &A, int tile_id, i
 // piece 16-byte aligned) and, with the fused blend, RGBA output; the caller falls back to fill_tile_rows otherwise.
 // (The per-wavefront row loop of fill_tile_rows issues 48 partly filled store instructions per tile; a fill workgroup
 // lived 13 us at 512^2 and kept its slot from the occupied tiles of a crowded XCD: tools/fine_timing.py.)
+//
+// WT (DSS_OPT_FORWARD_FILL = 1): every piece is a WRITE-THROUGH 16-byte store (sc1): the line leaves the XCD's L2 while the tile
+// workgroups still run instead of waiting there, dirty, for the write-back at the end of the launch.  Nothing in the launch
+// reads these bytes, and the kernel boundary orders them before every later reader as it does plain stores: no fence, no wait.
+// (A 16-byte sc1 store costs what a plain one does; the 4-byte stores of fill_tile_rows and of the occupied tiles would cost
+// ~6x per byte and stay plain.)  Same values, same addresses as WT = false.
+typedef int fill_piece __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ fill_piece fill_bits(const int4 v) { return fill_piece{v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ fill_piece fill_bits(const float4 v) { return fill_piece{__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), __float_as_int(v.w)}; }
+template <bool WT, typename T, typename V>
+__device__ __forceinline__ void fill_store16(T *p, const V v)
+{
+    if (WT) {
+        // the compiler neither counts this store nor pads behind it: nobody waits for it (the wavefront only ends), and the
+        // s_nop keeps the next instruction off the data registers until the store has read them
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(fill_bits(v)) : "memory");
+    } else {
+        *reinterpret_cast<V *>(p) = v;
+    }
+}
+
+template <bool WT>
 __device__ __forceinline__ void fill_tiles(const FineArgs &A, int t0, unsigned empty, int tid)
 {
     const TileGrid g = A.g;
@@ -1138,9 +1160,9 @@ __device__ __forceinline__ void fill_tiles(const FineArgs &A, int t0, unsigned e
         const int valid_rows = min(DSS_TILE, g.rows - ty * DSS_TILE);
         size_t o = (((size_t)n * g.rows + (size_t)ty * DSS_TILE) * S + (size_t)tx * DSS_TILE) * K + (size_t)e * 4;
         for (int r = 0; r < valid_rows; ++r, o += (size_t)S * K) {
-            *reinterpret_cast<int4 *>(A.idx + o) = m1i;
-            if (A.zbuf) *reinterpret_cast<float4 *>(A.zbuf + o) = m1f;
-            *reinterpret_cast<float4 *>(A.qv + o) = m1f;
+            fill_store16<WT>(A.idx + o, m1i);
+            if (A.zbuf) fill_store16<WT>(A.zbuf + o, m1f);
+            fill_store16<WT>(A.qv + o, m1f);
         }
     }
     // per-pixel planes: occupancy (2 pieces per tile row) and, with the fused blend, weight sum (2) + RGBA (8)
@@ -1158,13 +1180,13 @@ __device__ __forceinline__ void fill_tiles(const FineArgs &A, int t0, unsigned e
         const size_t pix = ((size_t)n * g.rows + (size_t)ty * DSS_TILE) * S + (size_t)tx * DSS_TILE;
         if (e < 2) {
             float *o = A.occ + pix + 4 * e;
-            for (int r = 0; r < valid_rows; ++r, o += S) *reinterpret_cast<float4 *>(o) = z4;
+            for (int r = 0; r < valid_rows; ++r, o += S) fill_store16<WT>(o, z4);
         } else if (e < 4) {
             float *o = A.wsum + pix + 4 * (e - 2);
-            for (int r = 0; r < valid_rows; ++r, o += S) *reinterpret_cast<float4 *>(o) = w4;
+            for (int r = 0; r < valid_rows; ++r, o += S) fill_store16<WT>(o, w4);
         } else {
             float *o = A.image + (size_t)n * A.img_sn + (size_t)(ty * DSS_TILE) * A.img_sr + (size_t)(tx * DSS_TILE + (e - 4)) * 4;
-            for (int r = 0; r < valid_rows; ++r, o += A.img_sr) *reinterpret_cast<float4 *>(o) = z4;
+            for (int r = 0; r < valid_rows; ++r, o += A.img_sr) fill_store16<WT>(o, z4);
         }
     }
 }
@@ -1781,7 +1803,7 @@ __host__ __device__ __forceinline__ uint32_t fill_workgroups(int total_tiles)
     return (((uint32_t)total_tiles + FILL_TILES - 1u) / FILL_TILES + 7u) & ~7u;
 }
 
-template <int KMAX, bool PACKED>
+template <int KMAX, bool PACKED, bool FILL_WT>
 #ifdef DSS_FINE_OCC8   // (A/B builds: eight wavefronts per SIMD, i.e. at most 64 VGPRs -- the kernel needs 69, seven wavefronts.  Measured at
                        //  the end of round 6: 7 VGPR spills, the step +2 % at configs[1], +2 % at configs[3], +2 % at configs[4]: not taken)
 __global__ __launch_bounds__(FINE_THREADS) __attribute__((amdgpu_num_sgpr(96))) __attribute__((amdgpu_waves_per_eu(8, 8))) void fine_kernel(const FineArgs A)
@@ -1834,7 +1856,7 @@ __global__ __launch_bounds__(FINE_THREADS) __attribute__((amdgpu_num_sgpr(96))) 
         const uintptr_t bits = (uintptr_t)A.idx | (uintptr_t)A.zbuf | (uintptr_t)A.qv | (uintptr_t)A.occ | (uintptr_t)A.image |
                                (uintptr_t)A.wsum | (uintptr_t)((A.img_sn | A.img_sr) * 4);
         if ((A.g.S & 7) == 0 && (bits & 15) == 0 && (A.image == nullptr || A.C == 3)) {
-            fill_tiles(A, t0, empty, tid);
+            fill_tiles<FILL_WT>(A, t0, empty, tid);
         } else {
 #pragma unroll 1
             for (int i = wid; i < FILL_TILES; i += FINE_WAVES)
@@ -1958,33 +1980,45 @@ static int fine_grid(const FineArgs &A, int blocks)
     return A.queue.list ? (int)(A.spill_wgs + A.queue_wgs + fill_workgroups(blocks)) : blocks;
 }
 
-template <int KMAX>
+template <int KMAX, bool FILL_WT>
 static void launch_fine(const FineArgs &A, int blocks, hipStream_t st)
 {
     if (KMAX <= 8 && A.rec != nullptr && A.image != nullptr && A.C == 3)
-        hipLaunchKernelGGL((fine_kernel<(KMAX <= 8 ? KMAX : 8), true>), dim3(fine_grid(A, blocks)), dim3(FINE_THREADS), 0, st, A);
+        hipLaunchKernelGGL((fine_kernel<(KMAX <= 8 ? KMAX : 8), true, FILL_WT>), dim3(fine_grid(A, blocks)), dim3(FINE_THREADS), 0, st, A);
     else
-        hipLaunchKernelGGL((fine_kernel<KMAX, false>), dim3(fine_grid(A, blocks)), dim3(FINE_THREADS), 0, st, A);
+        hipLaunchKernelGGL((fine_kernel<KMAX, false, FILL_WT>), dim3(fine_grid(A, blocks)), dim3(FINE_THREADS), 0, st, A);
+}
+// fill_wt: the instantiation whose fill workgroups store write-through (DSS_OPT_FORWARD_FILL = 1, dss_render_forward only).  A
+// template parameter and not a FineArgs field: FILL_WT = false is the kernel of before, instruction for instruction, and the
+// kernarg segment is unchanged.  (As a field with both fill_tiles inlined side by side, the tile path of every instantiation
+// was re-scheduled; behind a __noinline__ call the kernel took the callee's 86 VGPRs and 96 bytes of scratch:
+// profiles/forward_fill_ab.txt.)  With FILL_WT = true the source of the tile path is the same; the register allocator,
+// which spills SGPRs to VGPR lanes in this kernel, moves -31 .. +75 of its ~4,400 instructions, occupancy unchanged.
+template <int KMAX>
+static void launch_fine(const FineArgs &A, int blocks, bool fill_wt, hipStream_t st)
+{
+    if (fill_wt) launch_fine<KMAX, true>(A, blocks, st);
+    else launch_fine<KMAX, false>(A, blocks, st);
 }
 
-static bool dispatch_fine(const FineArgs &A, int blocks, hipStream_t st)
+static bool dispatch_fine(const FineArgs &A, int blocks, hipStream_t st, bool fill_wt = false)
 {
     const int K = A.K;
     switch (K) {
-        case 1: launch_fine<1>(A, blocks, st); return true;
-        case 2: launch_fine<2>(A, blocks, st); return true;
-        case 3: launch_fine<3>(A, blocks, st); return true;
-        case 4: launch_fine<4>(A, blocks, st); return true;
-        case 5: launch_fine<5>(A, blocks, st); return true;
-        case 6: launch_fine<6>(A, blocks, st); return true;
-        case 7: launch_fine<7>(A, blocks, st); return true;
-        case 8: launch_fine<8>(A, blocks, st); return true;
+        case 1: launch_fine<1>(A, blocks, fill_wt, st); return true;
+        case 2: launch_fine<2>(A, blocks, fill_wt, st); return true;
+        case 3: launch_fine<3>(A, blocks, fill_wt, st); return true;
+        case 4: launch_fine<4>(A, blocks, fill_wt, st); return true;
+        case 5: launch_fine<5>(A, blocks, fill_wt, st); return true;
+        case 6: launch_fine<6>(A, blocks, fill_wt, st); return true;
+        case 7: launch_fine<7>(A, blocks, fill_wt, st); return true;
+        case 8: launch_fine<8>(A, blocks, fill_wt, st); return true;
         default: break;
     }
-    if (K <= 12) { launch_fine<12>(A, blocks, st); return true; }
-    if (K <= 16) { launch_fine<16>(A, blocks, st); return true; }
-    if (K <= 24) { launch_fine<24>(A, blocks, st); return true; }
-    if (K <= 32) { launch_fine<32>(A, blocks, st); return true; }
+    if (K <= 12) { launch_fine<12>(A, blocks, fill_wt, st); return true; }
+    if (K <= 16) { launch_fine<16>(A, blocks, fill_wt, st); return true; }
+    if (K <= 24) { launch_fine<24>(A, blocks, fill_wt, st); return true; }
+    if (K <= 32) { launch_fine<32>(A, blocks, fill_wt, st); return true; }
     if (K <= DSS_MAX_K) {
         hipLaunchKernelGGL(fine_generic_kernel, dim3(blocks), dim3(64), 0, st, A);
         return true;
@@ -2513,6 +2547,6 @@ extern "C" int dss_render_forward(const float *world, const float *normals, cons
     // per step for a pass that is empty in the common case); a fine-only re-run finds the pool filled
     A.spill_wgs = s.rerun ? 0u : spill_workgroups_in_fine(P);
     A.spill_sorted = sorted ? 1 : 0;
-    if (!dispatch_fine(A, N * tiles, st)) { set_error("dss_render_forward: no kernel for K=%d", K); return DSS_ERR_UNSUPPORTED; }
+    if (!dispatch_fine(A, N * tiles, st, option(DSS_OPT_FORWARD_FILL) == 1)) { set_error("dss_render_forward: no kernel for K=%d", K); return DSS_ERR_UNSUPPORTED; }
     return check_launch("dss_render_forward");
 }

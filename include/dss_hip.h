@@ -12,7 +12,7 @@
  *   - work is enqueued asynchronously on `stream` (a hipStream_t; NULL = default stream); no host
  *     synchronisation happens inside the library; re-entrant; no environment variable is read and no
  *     hidden global state is kept: the only process-wide state is the explicit option table of
- *     dss_set_option() below (tuning hints, all 0 by default) and a per-device-ordinal cache of
+ *     dss_set_option() below (tuning hints, 0 by default unless stated) and a per-device-ordinal cache of
  *     device properties (CU count, occupancy), filled with atomics on first use;
  *   - return value: 0 on success, negative DSS_ERR_* otherwise (no exceptions cross the ABI);
  *     dss_last_error() returns a thread-local message for the last failing call on this thread;
@@ -89,6 +89,11 @@ DSS_API const char *dss_last_error(void);
  *   DSS_OPT_MESH_LARGE      dss_point_face_distance: triangles whose radius exceeds value / 4 grid cells are tested by
  *                             every query of their mesh instead of through the grid; 0 (default) = 8 (two cells), up to
  *                             4096.  For A/B measurements (tools/mesh_distance_timing.py).  Results do not depend on it.
+ *   DSS_OPT_FORWARD_FILL    how dss_render_forward's fine launch writes the constants of the tiles no splat reaches (the
+ *                             aligned 16-byte pieces of fill_tiles; the row-wise fallback is always plain): 0 = plain
+ *                             stores, 1 (default) = write-through stores, which leave the L2 while the occupied tiles are
+ *                             still being computed instead of at the end of the launch.  For A/B measurements and so that
+ *                             a test can reach both forms.  Results do not depend on it.
  * Returns DSS_ERR_INVALID_ARGUMENT for an unknown option or value. */
 #define DSS_OPT_LEAN_WORKSPACE 0
 #define DSS_OPT_BACKWARD_TPW 1
@@ -97,7 +102,8 @@ DSS_API const char *dss_last_error(void);
 #define DSS_OPT_KNN_QUERY 4
 #define DSS_OPT_BACKWARD_GRID 5
 #define DSS_OPT_MESH_LARGE 6
-#define DSS_OPT_COUNT 7
+#define DSS_OPT_FORWARD_FILL 7
+#define DSS_OPT_COUNT 8
 DSS_API int dss_band_rows(int row0, int row1, int row_cycle); /* rows of a band tensor (see `row_cycle` above) */
 DSS_API int dss_set_option(int option, int value);
 DSS_API int dss_get_option(int option);
