@@ -50,4 +50,7 @@ def __getattr__(name):
     if name == "evaluate_cloud":   # the reference's evaluation row (dss_amd/evaluation.py), imported on first use likewise
         from .evaluation import evaluate_cloud
         return evaluate_cloud
+    if name == "render_mesh_targets":   # target images, masks and depth from a mesh (dss_amd/mesh_render.py), likewise
+        from .mesh_render import render_mesh_targets
+        return render_mesh_targets
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -98,6 +98,22 @@ __device__ __forceinline__ void cam_to_lanes(CamWave &c)
     c.zn = lanes_of(c.zn); c.zf = lanes_of(c.zf); c.hc = lanes_of(c.hc);
 }
 
+// World position -> screen, stated once for the cloud points (setup_point_arith below) and for the vertices of a mesh
+// (mesh_raster.hip): a vertex and a point at the same position get the same bits.  View z, component j of the clip row, and
+// an NDC coordinate from a clip component and w = clip[3].  (Functions that return their value: with these the setup kernels
+// compile to the instructions they had when the expressions stood inline.)
+template <class Cam>
+__device__ __forceinline__ float project_view_z(const Cam &cam, float ph0, float ph1, float ph2, float ph3)
+{
+    return ph0 * cam.v(2) + ph1 * cam.v(6) + ph2 * cam.v(10) + ph3 * cam.v(14);
+}
+template <class Cam>
+__device__ __forceinline__ float project_clip(const Cam &cam, int j, float ph0, float ph1, float ph2, float ph3)
+{
+    return ph0 * cam.m(j) + ph1 * cam.m(4 + j) + ph2 * cam.m(8 + j) + ph3 * cam.m(12 + j);
+}
+__device__ __forceinline__ float project_ndc(float c, float w) { return c / w; }
+
 // What the setup reads of its point before the arithmetic starts.
 struct SetupIn {
     float ph0, ph1, ph2, n0, n1, n2;   // world position, cloud normal (row wi of world / normals)
@@ -133,7 +149,7 @@ __device__ __forceinline__ SetupVals setup_point_arith(const SetupArgs &A, int64
         asm volatile("" ::"v"(ph0), "v"(ph2), "v"(n0), "v"(n2));   // (the inputs have arrived)
         DSS_SETUP_MARK(7);
 #endif
-        const float zview = ph0 * cam.v(2) + ph1 * cam.v(6) + ph2 * cam.v(10) + ph3 * cam.v(14);
+        const float zview = project_view_z(cam, ph0, ph1, ph2, ph3);
         // _filter_points_with_invalid_depth, rasterizer.py:183-217
         ok = (zview >= cam.znear()) && (zview <= cam.zfar());
         if (A.backface) {
@@ -145,10 +161,10 @@ __device__ __forceinline__ SetupVals setup_point_arith(const SetupArgs &A, int64
         if (ok) {
             float clip[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) clip[j] = ph0 * cam.m(j) + ph1 * cam.m(4 + j) + ph2 * cam.m(8 + j) + ph3 * cam.m(12 + j);
+            for (int j = 0; j < 4; ++j) clip[j] = project_clip(cam, j, ph0, ph1, ph2, ph3);
             const float w = clip[3];
-            sx = clip[0] / w;
-            sy = clip[1] / w;
+            sx = project_ndc(clip[0], w);
+            sy = project_ndc(clip[1], w);
             sz = zview;
             const float dw = eps_denom_py(w), dw2 = eps_denom_py(w * w);
             float WJ[3][2];

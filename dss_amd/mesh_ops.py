@@ -1,9 +1,13 @@
-"""Operators between packed clouds and packed triangle meshes: the nearest face of mesh n for every point of cloud n
+"""Operators on packed triangle meshes.  Between packed clouds and packed meshes: the nearest face of mesh n for every point of cloud n
 (``dss_point_face_distance``), the nearest point of cloud n for every face of mesh n (``dss_face_point_distance``) and the
 gradient of both (``dss_mesh_distance_backward``) -- the p2f columns of the reference's evaluation row
 (scripts/evaluatePointClouds.py:52,103-132) and ``pytorch3d.loss.point_mesh_face_distance``.  The distance is defined once
 in include/dss_hip.h.  Re-exported by `dss_amd.ops`; written like `cross_cloud.py` and entering the library the same way,
 through `_lib.call`: tensors checked by `_lib.require_gpu`, no CPU fallback.
+
+Meshes to target images (``dss_rasterize_meshes``, ``dss_mesh_flat_shade``): `rasterize_meshes`, `shade_mesh_flat` -- the
+hard rasteriser and the flat shader of the reference's data script (scripts/create_mvr_data_from_mesh.py:148-219), forward
+only, under the coverage and depth rule stated once in include/dss_hip.h.
 """
 import torch
 
@@ -107,3 +111,86 @@ def mesh_distance_backward(points, p_first, p_num, verts, faces, f_first, f_num,
         _lib.call("dss_mesh_distance_backward", dev, points, pf, pn, P, verts, V, faces, ff, fn, F, N, idx_pf, idx_fp, order_f,
                   order_v, g_p, g_f, grad_points, grad_verts)
     return grad_points, grad_verts
+
+
+def _mesh_cameras(who, verts, faces, f_first, f_num, N, shared_mesh):
+    verts, = _gpu(_f32, verts=verts)
+    faces, ff, fn = _gpu(_i64, faces=faces, f_first=f_first, f_num=f_num)
+    if (verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or ff.dim() != 1 or fn.shape != ff.shape
+            or ff.shape[0] != (1 if shared_mesh else N) or faces.device != verts.device):
+        raise RuntimeError("%s: verts (V,3) float32 and faces (F,3) int64 on one device, f_first / f_num (%s,), got %s"
+                           % (who, "1" if shared_mesh else "N=%d" % N, tuple(ff.shape)))
+    return verts, faces, ff, fn
+
+
+def _one_device(who, dev, **tensors):
+    """the entry dereferences every pointer on `dev`: a tensor of another GPU is refused here"""
+    for name, t in tensors.items():
+        if t.device != dev:
+            raise RuntimeError("%s: %s is on %s, verts on %s" % (who, name, t.device, dev))
+
+
+def rasterize_meshes(verts, faces, f_first, f_num, M, V, znear, zfar, cam_center, image_size: int, shared_mesh: bool = True,
+                     cull_backfaces: bool = False):
+    """Hard rasterisation of packed meshes for N cameras (``dss_rasterize_meshes``) -> ``pix_to_face`` (N,S,S) int64 =
+    the mesh-local id of the nearest covering face or -1, ``zbuf`` (N,S,S) its view depth or -1, ``bary`` (N,S,S,3) its
+    perspective-correct barycentrics or 0, ``screen_verts`` (N,V,3) = (NDC x, NDC y, view z) of every vertex under every
+    camera.  ``faces`` holds PACKED vertex ids; ``shared_mesh``: f_first / f_num (1,), all cameras see that one mesh,
+    otherwise (N,) and camera n sees mesh n.  ``M`` / ``V`` (N,4,4) are the full projection and world-to-view matrices
+    (row-vector convention), ``cam_center`` (N,3) is read for ``cull_backfaces`` only.  Inclusive edges, ties to the
+    smaller id, no clipping: the rule of include/dss_hip.h, bitwise reproducible."""
+    M, V, znear, zfar, cam_center = _gpu(_f32, M=M, V=V, znear=znear, zfar=zfar, cam_center=cam_center)
+    N, S = M.shape[0], int(image_size)
+    if M.shape != (N, 4, 4) or V.shape != (N, 4, 4) or znear.shape != (N,) or zfar.shape != (N,) or cam_center.shape != (N, 3):
+        raise RuntimeError("rasterize_meshes: M, V (N,4,4), znear, zfar (N,), cam_center (N,3) with N=%d" % N)
+    verts, faces, ff, fn = _mesh_cameras("rasterize_meshes", verts, faces, f_first, f_num, N, shared_mesh)
+    _one_device("rasterize_meshes", verts.device, f_first=ff, f_num=fn, M=M, V=V, znear=znear, zfar=zfar, cam_center=cam_center)
+    nV, nF, dev = verts.shape[0], faces.shape[0], verts.device
+    with _on_device(dev):
+        nbytes = _lib.load().dss_mesh_raster_workspace(N, nF, nV, S)
+        if nbytes == 0:
+            _lib.check(-1, "dss_mesh_raster_workspace")
+        pix_to_face = torch.empty((N, S, S), dtype=_i64, device=dev)
+        zbuf = torch.empty((N, S, S), dtype=_f32, device=dev)
+        bary = torch.empty((N, S, S, 3), dtype=_f32, device=dev)
+        screen_verts = torch.empty((N, nV, 3), dtype=_f32, device=dev)
+        ws = _lib.workspace(dev, nbytes)
+        _lib.call("dss_rasterize_meshes", dev, verts, nV, faces, ff, fn, nF, M, V, znear, zfar, cam_center, N, int(shared_mesh),
+                  int(cull_backfaces), S, pix_to_face, zbuf, bary, screen_verts, ws, ws.numel())
+    return pix_to_face, zbuf, bary, screen_verts
+
+
+def shade_mesh_flat(pix_to_face, bary, verts, faces, f_first, f_num, cam_center, ambient, diffuse_color, specular_color,
+                    light_vec, point_lights: bool, shininess: float = 64.0, background=(1.0, 1.0, 1.0), face_colors=None,
+                    shared_mesh: bool = True):
+    """Flat shading of `rasterize_meshes`' fragments (``dss_mesh_flat_shade``) -> ``rgba`` (N,S,S,4): on a covered pixel
+    ``colour * (ambient + diffuse) + specular`` of ``dss_phong_forward``'s formula at the interpolated world position with
+    the face normal normalize((B - A) x (C - A)), alpha 1; elsewhere ``background`` and alpha 0.  ``ambient`` (N,3),
+    ``diffuse_color`` / ``specular_color`` / ``light_vec`` (N,L,3) as `phong_forward` takes them; ``face_colors`` (F,3)
+    per packed face, default white.  Colours are not clamped."""
+    pix_to_face, = _gpu(_i64, pix_to_face=pix_to_face)
+    bary, cam_center, ambient, kd, ks, lv = _gpu(_f32, bary=bary, cam_center=cam_center, ambient=ambient,
+                                                 diffuse_color=diffuse_color, specular_color=specular_color, light_vec=light_vec)
+    N, S = pix_to_face.shape[0], pix_to_face.shape[-1]
+    L = kd.shape[1] if kd.dim() == 3 else -1
+    if (pix_to_face.shape != (N, S, S) or bary.shape != (N, S, S, 3) or cam_center.shape != (N, 3) or ambient.shape != (N, 3)
+            or kd.shape != (N, L, 3) or ks.shape != (N, L, 3) or lv.shape != (N, L, 3)):
+        raise RuntimeError("shade_mesh_flat: pix_to_face (N,S,S), bary (N,S,S,3), cam_center, ambient (N,3), light tensors "
+                           "(N,L,3) with N=%d" % N)
+    verts, faces, ff, fn = _mesh_cameras("shade_mesh_flat", verts, faces, f_first, f_num, N, shared_mesh)
+    _one_device("shade_mesh_flat", verts.device, f_first=ff, f_num=fn, pix_to_face=pix_to_face, bary=bary, cam_center=cam_center,
+                ambient=ambient, diffuse_color=kd, specular_color=ks, light_vec=lv)
+    if face_colors is not None:
+        face_colors, = _gpu(_f32, face_colors=face_colors)
+        if face_colors.shape != (faces.shape[0], 3):
+            raise RuntimeError("shade_mesh_flat: face_colors must be (F,3)")
+        _one_device("shade_mesh_flat", verts.device, face_colors=face_colors)
+    bg = [float(c) for c in background]
+    if len(bg) != 3:
+        raise RuntimeError("shade_mesh_flat: background must have 3 components")
+    dev = verts.device
+    with _on_device(dev):
+        rgba = torch.empty((N, S, S, 4), dtype=_f32, device=dev)
+        _lib.call("dss_mesh_flat_shade", dev, pix_to_face, bary, verts, verts.shape[0], faces, ff, fn, faces.shape[0], face_colors,
+                  N, int(shared_mesh), S, ambient, kd, ks, lv, L, int(bool(point_lights)), cam_center, float(shininess), *bg, rgba)
+    return rgba

@@ -1370,6 +1370,8 @@ def image_loss_band_backward_partials(rgba_band, target_rgb, target_mask, rows, 
 from .cross_cloud import chamfer_backward, chamfer_order, nearest_points, packed_cloud_ids  # noqa: E402,F401
 # likewise the operators between a cloud and a triangle mesh (mesh_ops.py: nearest face, nearest point of a face, backward)
 from .mesh_ops import face_point_distance, mesh_distance_backward, mesh_distance_orders, point_face_distance  # noqa: E402,F401
+# and the meshes' way to target images (mesh_ops.py: hard rasteriser, flat shader)
+from .mesh_ops import rasterize_meshes, shade_mesh_flat  # noqa: E402,F401
 # likewise the two kernels of an upsampling round (upsample_ops.py; the rounds themselves are dss_amd.cloud_ops.upsample)
 from .upsample_ops import upsample_candidates, upsample_insert  # noqa: E402,F401
 # and the two kernels that clean a cloud (smoothing_ops.py; the public calls are dss_amd.cloud_ops.denoise_normals and

@@ -65,7 +65,8 @@ class _Lights:
         return out
 
     def _packed(self, N):
-        """-> ambient (N,3) summed over lights (texture.py:50-54), kd, ks, vec (N,L,3)."""
+        """-> ambient (N,3) summed over lights (texture.py:50-54), kd, ks, vec (N,L,3).  Also what
+        `mesh_render.render_mesh_targets` hands to `ops.shade_mesh_flat`: keep the four and their shapes."""
         L = max(self.diffuse_color.shape[1], self.specular_color.shape[1], getattr(self, self._vec).shape[1])
         ex = lambda t: t.expand(N, L, 3).contiguous()
         amb = self.ambient_color.sum(dim=1).expand(N, 3).contiguous()

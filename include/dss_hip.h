@@ -648,6 +648,65 @@ DSS_API int dss_mesh_distance_backward(const float *points, const int64_t *p_fir
                                        float *grad_points /* (P,3) */, float *grad_verts /* (V,3) */, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Triangle meshes -> target images: the hard rasteriser and the flat shader of the reference's data script
+ * (scripts/create_mvr_data_from_mesh.py:148-219: pytorch3d's MeshRasterizer with blur_radius 0, of whose fragments the
+ * script reads slot 0 only, and HardFlatShader) [third party, not vendored; parity is to the definition below].  Forward
+ * only.  verts (V,3); faces (F,3) int64 PACKED vertex ids; shared_mesh = 1: f_first / f_num (1,), all N cameras see that
+ * mesh; otherwise (N,) and camera n sees mesh n.  M, V (N,4,4) as dss_point_setup takes them.
+ * The rule, fp32 without contraction, correctly rounded division, per camera n:
+ *   vertices      screen_verts[n][v] = (ndc x, ndc y, view z) by the device functions of the per-point setup (project_view_z,
+ *                 project_clip, project_ndc of csrc/setup_body.h): a vertex and a cloud point at one position get the same
+ *                 bits.  +X left, +Y up; image column c <-> NDC index S - 1 - c (rows alike); pixel centre
+ *                 -1 + (2 i + 1.0f) / S (pix_to_ndc).
+ *   absent faces  never an answer, vertices never read through a bad id: a packed vertex id outside [0, V); a non-finite
+ *                 screen_verts component; a vertex with view z outside [znear[n], zfar[n]] -- there is NO clipping, a face
+ *                 is drawn whole or not at all (DSS cameras stand outside the object); A == 0 (below); with
+ *                 cull_backfaces, dot((B - A) x (C - A), cam_center[n] - A) <= 0 in world space, dot = (x x + y y) + z z.
+ *   edge(a, b) at p   u = the endpoint with the lexicographically smaller screen (x, y) (by value), v = the other;
+ *                 e = (v.x - u.x) (p.y - u.y) - (v.y - u.y) (p.x - u.x), negated if the endpoints were swapped: two
+ *                 faces that share an edge, welded or not, get the same bits with opposite sign.
+ *   coverage      A = edge(p0, p1) at p2, s = sign(A); w0, w1, w2 = s edge(p1, p2), s edge(p2, p0), s edge(p0, p1) at the
+ *                 pixel centre; bs = (w0 + w1) + w2; covered iff every w >= 0 (INCLUSIVE: a centre on a shared edge belongs
+ *                 to both faces, the winner rule decides; pytorch3d's strict rule gives it to neither) and bs > 0.
+ *   pixels        a face is tested at the pixels of its rectangle: ndc_index_range (csrc/tile_rect.h) of
+ *                 ((min + max) * 0.5f, (max - min) * 0.5f) of its screen x and of its screen y, one pixel of slack a side.
+ *                 The fine kernel applies the rectangle per pixel, so it is the rule, not only a bound on the work.
+ *   depth         b_k = w_k / bs; q_k = b_k / z_k; t = (q0 + q1) + q2; zbuf = 1 / t; bary_k = q_k * zbuf.
+ *   winner        the covered face with the smallest zbuf under `<` (a NaN never wins), ties to the smaller mesh-local
+ *                 face id: independent of the order in which faces are visited, so a repeated call returns the same bits.
+ *   empty pixel   pix_to_face = -1, zbuf = -1, bary = 0.
+ * dss_rasterize_meshes: one record per (camera, face); a face whose rectangle meets at most 16 8x8 tiles is binned per
+ * tile (count, scan, fill; integer atomics hand out the slots), a larger one goes on its camera's list, which every tile
+ * tests against the face's rectangle; one wavefront per tile, one lane per pixel.  The result does not depend on the list
+ * a face travels on.  No float atomics, nothing is read back.  Workspace: dss_mesh_raster_workspace(N, F, V, S), known on
+ * the host (0 for sizes the entry refuses).  Any S >= 1.
+ * dss_mesh_flat_shade: per covered pixel x = (bary0 A + bary1 B) + bary2 C, the face normal (B - A) x (C - A) over its
+ * length, then dss_phong_forward's formula (csrc/phong.h) with rgb = face_colors[packed face] (NULL: white) ->
+ * rgba (N,S,S,4), 16-byte aligned, alpha 1; an empty pixel gets (bg_r, bg_g, bg_b, 0).  Colours are not clamped.  powf is
+ * why colours are not pinned to the bit.
+ * Refusals (DSS_ERR_INVALID_ARGUMENT, nothing launched; the limits beyond F, V < 2^31 and S >= 1 are deliberate, what the
+ * layout holds): N < 1 or N > 65535; F, V outside [0, 2^31); N F > 2^27 (record
+ * ids and list positions are 32-bit); N V > 2^31; S < 1 or S > 32768; L outside [0, 65535]; a NULL tensor that would be
+ * read or written.  A short or NULL workspace is DSS_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+DSS_API size_t dss_mesh_raster_workspace(int N, int64_t F, int64_t V, int S);
+DSS_API int dss_rasterize_meshes(const float *verts /* (V,3) */, int64_t V, const int64_t *faces /* (F,3) */,
+                                 const int64_t *f_first, const int64_t *f_num, int64_t F, const float *M /* (N,4,4) */,
+                                 const float *Vmat /* (N,4,4) */, const float *znear /* (N,) */, const float *zfar /* (N,) */,
+                                 const float *cam_center /* (N,3); read with cull_backfaces only */, int N, int shared_mesh,
+                                 int cull_backfaces, int S, int64_t *pix_to_face /* (N,S,S) */, float *zbuf /* (N,S,S) */,
+                                 float *bary /* (N,S,S,3) */, float *screen_verts /* (N,V,3) */, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+DSS_API int dss_mesh_flat_shade(const int64_t *pix_to_face /* (N,S,S) */, const float *bary /* (N,S,S,3) */,
+                                const float *verts /* (V,3) */, int64_t V, const int64_t *faces /* (F,3) */,
+                                const int64_t *f_first, const int64_t *f_num, int64_t F,
+                                const float *face_colors /* (F,3) or NULL */, int N, int shared_mesh, int S,
+                                const float *ambient /* (N,3) */, const float *diffuse_color /* (N,L,3) */,
+                                const float *specular_color /* (N,L,3) */, const float *light_vec /* (N,L,3) */, int L,
+                                int point_lights, const float *cam_center /* (N,3) */, float shininess, float bg_r,
+                                float bg_g, float bg_b, float *rgba /* (N,S,S,4) */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * One round of sparsity upsampling: `upsample` of DSS/core/cloud.py:555-632 inserts points where a neighbourhood is
  * sparsest, a tenth of the cloud per round.  The reference materialises an (N,P,K,K,3) tensor; here one kernel searches the
  * K x K candidates of every point and a second one assembles the grown cloud.  Between them the caller sorts `key` (one
