@@ -53,4 +53,7 @@ def __getattr__(name):
     if name == "render_mesh_targets":   # target images, masks and depth from a mesh (dss_amd/mesh_render.py), likewise
         from .mesh_render import render_mesh_targets
         return render_mesh_targets
+    if name in ("sample_points_from_meshes", "sample_mesh_evenly"):   # points on a mesh's surface (dss_amd/mesh_sampling.py)
+        from . import mesh_sampling
+        return getattr(mesh_sampling, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

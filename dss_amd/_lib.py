@@ -109,6 +109,10 @@ SIGNATURES = {
                              + [_c_vp, _c_sz, _c_vp]),
     "dss_mesh_flat_shade": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_int, _c_int]
                             + [_c_vp] * 4 + [_c_int, _c_int, _c_vp, _c_f32, _c_f32, _c_f32, _c_f32, _c_vp, _c_vp]),
+    "dss_mesh_sample_workspace": (_c_sz, [_c_int, _c_i64]),
+    "dss_sample_mesh_surface": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_i64, ctypes.c_uint64] + [_c_vp] * 4
+                                + [_c_vp, _c_sz, _c_vp]),
+    "dss_mesh_sample_backward": (_c_int, [_c_vp] * 3 + [_c_i64, _c_int, _c_i64, _c_i64] + [_c_vp] * 5 + [_c_vp]),
     "dss_upsample_candidates": (_c_int, [_c_vp] * 4 + [_c_int, _c_i64, _c_int] + [_c_vp] * 3 + [_c_vp]),
     "dss_upsample_insert": (_c_int, [_c_vp, _c_vp, _c_int] + [_c_vp] * 8 + [_c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp,
                                                                            _c_vp]),

@@ -19,10 +19,12 @@ def _one_cloud(t, name):
     return t, torch.zeros(1, dtype=torch.int64, device=dev), torch.full((1,), t.shape[0], dtype=torch.int64, device=dev)
 
 
-def evaluate_cloud(pred, gt_cloud=None, gt_mesh=None):
+def evaluate_cloud(pred, gt_cloud=None, gt_mesh=None, gt_samples=None, seed=0):
     """The reference script's row for ``pred`` (P,3) -> dict of 0-dim device tensors (no host read):
 
-    ``"CD"``         mean squared nearest-point distance pred -> gt plus gt -> pred (with ``gt_cloud`` (Q,3))
+    ``"CD"``         mean squared nearest-point distance pred -> gt plus gt -> pred (with ``gt_cloud`` (Q,3); without one,
+                     with ``gt_mesh`` and an int ``gt_samples``, against that many surface samples of the mesh:
+                     `ops.sample_mesh_surface` under ``seed``)
     ``"hausdorff"``  the two maxima of those squared distances, SUMMED as evaluatePointClouds.py:114-115 does (a quirk of the
                      script, kept: the textbook Hausdorff distance is their maximum, of unsquared distances)
     ``"p2f avg"``, ``"p2f std"``  mean and population standard deviation of sqrt(d2) from `ops.point_face_distance`
@@ -30,6 +32,14 @@ def evaluate_cloud(pred, gt_cloud=None, gt_mesh=None):
     Keys whose ground truth is not given are absent."""
     x, xf, xn = _one_cloud(pred, "pred")
     row = {}
+    if gt_cloud is None and gt_mesh is not None and gt_samples is not None:
+        verts, faces = gt_mesh
+        dev = x.device
+        faces = faces.to(torch.int64).contiguous()
+        gt_cloud = ops.sample_mesh_surface(verts.detach().to(torch.float32).contiguous(), faces,
+                                           torch.zeros(1, dtype=torch.int64, device=dev),
+                                           torch.full((1,), faces.shape[0], dtype=torch.int64, device=dev), int(gt_samples),
+                                           int(seed), want_normals=False, want_bary=False)[0][0]
     if gt_cloud is not None:
         y, yf, yn = _one_cloud(gt_cloud, "gt_cloud")
         d_xy, _ = ops.nearest_points(x, xf, xn, y, yf, yn)

@@ -8,6 +8,11 @@ through `_lib.call`: tensors checked by `_lib.require_gpu`, no CPU fallback.
 Meshes to target images (``dss_rasterize_meshes``, ``dss_mesh_flat_shade``): `rasterize_meshes`, `shade_mesh_flat` -- the
 hard rasteriser and the flat shader of the reference's data script (scripts/create_mvr_data_from_mesh.py:148-219), forward
 only, under the coverage and depth rule stated once in include/dss_hip.h.
+
+Points on a mesh's surface (``dss_sample_mesh_surface``, ``dss_mesh_sample_backward``): `sample_mesh_surface`,
+`mesh_sample_backward` -- the area-weighted sampler of that script's ground-truth cloud (:174-181), under the rule stated
+once in include/dss_hip.h: integer area keys and a counter-based generator, so a result is a function of the inputs and
+the seed alone.
 """
 import torch
 
@@ -194,3 +199,83 @@ def shade_mesh_flat(pix_to_face, bary, verts, faces, f_first, f_num, cam_center,
         _lib.call("dss_mesh_flat_shade", dev, pix_to_face, bary, verts, verts.shape[0], faces, ff, fn, faces.shape[0], face_colors,
                   N, int(shared_mesh), S, ambient, kd, ks, lv, L, int(bool(point_lights)), cam_center, float(shininess), *bg, rgba)
     return rgba
+
+
+def _sample_meshes(who, faces, f_first, f_num):
+    faces, ff, fn = _gpu(_i64, faces=faces, f_first=f_first, f_num=f_num)
+    if faces.dim() != 2 or faces.shape[1] != 3 or ff.dim() != 1 or fn.shape != ff.shape:
+        raise RuntimeError("%s: faces (F,3) int64, f_first / f_num (N,), got %s, %s, %s" % (who, tuple(faces.shape), tuple(ff.shape),
+                                                                                           tuple(fn.shape)))
+    _one_device(who, faces.device, f_first=ff, f_num=fn)
+    return faces, ff, fn
+
+
+def sample_mesh_surface(verts, faces, f_first, f_num, num_samples: int, seed: int, want_normals: bool = True,
+                        want_bary: bool = True):
+    """``num_samples`` area-weighted random points of every mesh of a packed batch (``dss_sample_mesh_surface``) ->
+    ``points`` (N,S,3), ``normals`` (N,S,3) = the unit normal (B - A) x (C - A) of the sample's face or None, ``face_idx``
+    (N,S) int64 mesh-local, ``bary`` (N,S,3) the weights of the face's three corners or None.  ``faces`` holds PACKED vertex
+    ids.  Philox4x32-10 on (sample, mesh) under the 64-bit ``seed`` and integer area keys: the rule of include/dss_hip.h, a
+    function of the inputs and the seed alone, bitwise reproducible.  A face with a bad vertex id or a non-finite vertex is
+    absent and a face below 2^-32 of its mesh's largest is never drawn; a mesh with nothing to sample gets points, normals
+    and bary 0 and face_idx -1."""
+    verts, = _gpu(_f32, verts=verts)
+    faces, ff, fn = _sample_meshes("sample_mesh_surface", faces, f_first, f_num)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError("sample_mesh_surface: verts must be (V,3), got %s" % (tuple(verts.shape),))
+    _one_device("sample_mesh_surface", verts.device, faces=faces)
+    N, S, V, F, dev = ff.shape[0], int(num_samples), verts.shape[0], faces.shape[0], verts.device
+    if S < 0:
+        raise RuntimeError("sample_mesh_surface: num_samples must not be negative, got %d" % S)
+    with _on_device(dev):
+        if N == 0 or S == 0 or F == 0:   # nothing to launch: the rows of a mesh with nothing to sample are made here
+            points = torch.zeros((N, S, 3), dtype=_f32, device=dev)
+            normals = torch.zeros((N, S, 3), dtype=_f32, device=dev) if want_normals else None
+            bary = torch.zeros((N, S, 3), dtype=_f32, device=dev) if want_bary else None
+            return points, normals, torch.full((N, S), -1, dtype=_i64, device=dev), bary
+        nbytes = _lib.load().dss_mesh_sample_workspace(N, F)
+        if nbytes == 0:
+            _lib.check(-1, "dss_mesh_sample_workspace")
+        points = torch.empty((N, S, 3), dtype=_f32, device=dev)
+        normals = torch.empty((N, S, 3), dtype=_f32, device=dev) if want_normals else None
+        face_idx = torch.empty((N, S), dtype=_i64, device=dev)
+        bary = torch.empty((N, S, 3), dtype=_f32, device=dev) if want_bary else None
+        ws = _lib.workspace(dev, nbytes)
+        _lib.call("dss_sample_mesh_surface", dev, verts, V, faces, ff, fn, F, N, S, int(seed) & 0xFFFFFFFFFFFFFFFF, points, normals,
+                  face_idx, bary, ws, ws.numel())
+    return points, normals, face_idx, bary
+
+
+def mesh_sample_order(faces, f_first, f_num, V, face_idx):
+    """The contributor list of ``dss_mesh_sample_backward`` (stable `torch.sort` of int64 keys, as `mesh_distance_orders`):
+    the entries 3 (n S + s) + corner by (packed id of the vertex at that corner, entry), entries of no face last."""
+    F = faces.shape[0]
+    f = f_first[:, None] + face_idx
+    ok = (face_idx >= 0) & (face_idx < f_num[:, None]) & (f >= 0) & (f < F)
+    if F > 0:
+        vid = faces[f.clamp(min=0, max=F - 1)]                      # (N,S,3); rows of samples without a face are masked below
+    else:
+        vid = torch.full(tuple(face_idx.shape) + (3,), -1, dtype=_i64, device=faces.device)
+    key = torch.where(ok[..., None] & (vid >= 0) & (vid < V), vid, torch.full_like(vid, _NO_KEY))
+    return torch.sort(key.reshape(-1), stable=True).indices
+
+
+def mesh_sample_backward(faces, f_first, f_num, V: int, face_idx, bary, g_points):
+    """Gradient of `sample_mesh_surface`'s points w.r.t. the vertices (``dss_mesh_sample_backward``) with ``face_idx`` and
+    ``bary`` held constant, ``g_points`` (N,S,3) = d loss / d points -> grad_verts (V,3), fully written, bitwise
+    reproducible (no atomics: see `mesh_sample_order`).  The normals carry no gradient."""
+    faces, ff, fn = _sample_meshes("mesh_sample_backward", faces, f_first, f_num)
+    face_idx, = _gpu(_i64, face_idx=face_idx)
+    bary, g_points = _gpu(_f32, bary=bary, g_points=g_points)
+    N, V, dev = ff.shape[0], int(V), faces.device
+    S = face_idx.shape[1] if face_idx.dim() == 2 else -1
+    if face_idx.shape != (N, S) or bary.shape != (N, S, 3) or g_points.shape != (N, S, 3) or V < 0:
+        raise RuntimeError("mesh_sample_backward: face_idx (N,S), bary and g_points (N,S,3) with N=%d, V >= 0" % N)
+    _one_device("mesh_sample_backward", dev, face_idx=face_idx, bary=bary, g_points=g_points)
+    with _on_device(dev):
+        if N == 0 or V == 0 or S == 0 or faces.shape[0] == 0:
+            return torch.zeros((V, 3), dtype=_f32, device=dev)
+        order = mesh_sample_order(faces, ff, fn, V, face_idx)
+        grad_verts = torch.empty((V, 3), dtype=_f32, device=dev)
+        _lib.call("dss_mesh_sample_backward", dev, faces, ff, fn, faces.shape[0], N, S, V, face_idx, bary, order, g_points, grad_verts)
+    return grad_verts

@@ -1,7 +1,8 @@
 """Target images from a triangle mesh: what the reference's data script renders per view
 (scripts/create_mvr_data_from_mesh.py:148-219 -- pytorch3d's MeshRasterizer with blur_radius 0 and HardFlatShader, a hard
 mask, a dense depth map with zfar off the surface), on the GPU through `ops.rasterize_meshes` and `ops.shade_mesh_flat`.
-Forward only: a target image needs no gradient.  File formats and the sampling of the surface stay with the caller."""
+Forward only: a target image needs no gradient.  The script's ground-truth cloud (:174-181) is
+`dss_amd.mesh_sampling.sample_points_from_meshes`; file formats stay with the caller."""
 import torch
 
 from . import ops

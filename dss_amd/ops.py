@@ -1372,6 +1372,9 @@ from .cross_cloud import chamfer_backward, chamfer_order, nearest_points, packed
 from .mesh_ops import face_point_distance, mesh_distance_backward, mesh_distance_orders, point_face_distance  # noqa: E402,F401
 # and the meshes' way to target images (mesh_ops.py: hard rasteriser, flat shader)
 from .mesh_ops import rasterize_meshes, shade_mesh_flat  # noqa: E402,F401
+# and the points on a mesh's surface (mesh_ops.py: the sampler and its backward; the public calls are
+# dss_amd.mesh_sampling.sample_points_from_meshes and sample_mesh_evenly)
+from .mesh_ops import mesh_sample_backward, mesh_sample_order, sample_mesh_surface  # noqa: E402,F401
 # likewise the two kernels of an upsampling round (upsample_ops.py; the rounds themselves are dss_amd.cloud_ops.upsample)
 from .upsample_ops import upsample_candidates, upsample_insert  # noqa: E402,F401
 # and the two kernels that clean a cloud (smoothing_ops.py; the public calls are dss_amd.cloud_ops.denoise_normals and

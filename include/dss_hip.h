@@ -707,6 +707,57 @@ DSS_API int dss_mesh_flat_shade(const int64_t *pix_to_face /* (N,S,S) */, const 
                                 float bg_g, float bg_b, float *rgba /* (N,S,S,4) */, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Surface samples of a triangle mesh: S area-weighted random points of every mesh of a packed batch, with the face normal,
+ * the face and the barycentric weights of each -- the ground-truth cloud of the reference's data script
+ * (scripts/create_mvr_data_from_mesh.py:174-181) and the initial cloud of config.py:179, there
+ * pytorch3d.ops.sample_points_from_meshes [third party, not vendored; parity is to the definition below: the same
+ * distribution, not the same draws].  verts (V,3); faces (F,3) int64 PACKED vertex ids; packed meshes with f_first / f_num
+ * (N,); S samples for every mesh; a 64-bit seed.  A mesh whose range does not lie within [0, F) has no face.
+ * The rule, fp32 without contraction, correctly rounded sqrtf and division; a result is a pure function of the inputs and
+ * the seed, whatever the launch shape:
+ *   face weight   nrm = (B - A) x (C - A), len = sqrtf((nx nx + ny ny) + nz nz) in the operations and order of
+ *                 dss_mesh_flat_shade (without its clamp).  ABSENT faces get len = 0: a packed vertex id outside [0, V) (the
+ *                 vertices are never read through a bad id), a non-finite vertex, a non-finite len (an overflowed +inf
+ *                 never reaches the ldexp below).
+ *   integer key   len_max = the largest len of the mesh (a maximum is order-free), frexp(len_max) = (m, e);
+ *                 key_f = (uint64) floor(ldexp((double) len_f, 32 - e)): scaled by a power of two, so exact; every key is
+ *                 <= 2^32 and the largest face's >= 2^31.  A face whose area is below 2^-32 of the mesh's largest face has
+ *                 key 0 and is NEVER drawn.  cum = the inclusive sums of the keys within the mesh in uint64, total = the
+ *                 last one: integer sums, so any parallel scan gives the same bits.
+ *   random words  Philox4x32-10 (csrc/philox.h; multipliers 0xD2511F53, 0xCD9E8D57, Weyl 0x9E3779B9, 0xBB67AE85), counter
+ *                 (s & 0xFFFFFFFF, s >> 32, n, 0) for sample s of mesh n (the fourth word is reserved as a stream id), key
+ *                 (seed & 0xFFFFFFFF, seed >> 32) -> r0 .. r3.  Sample s depends on neither S nor any other sample.
+ *   face          target = umul64hi((r0 << 32) | r1, total), in [0, total); the face is the first f of the mesh with
+ *                 cum[f] > target (upper bound): a key-0 face is never chosen.  face_idx is mesh-local.
+ *   position      u1 = (r2 >> 8) 2^-24, u2 = (r3 >> 8) 2^-24, both in [0, 1); su = sqrtf(u1); bary = (1 - su,
+ *                 su (1 - u2), su u2); point = (bary0 A + bary1 B) + bary2 C per component, the expression of
+ *                 dss_mesh_flat_shade; normal = nrm / len per component.
+ *   nothing to sample  (f_num = 0, every face absent or degenerate, total = 0): every sample of the mesh is point 0,
+ *                 normal 0, bary 0, face_idx -1.  Outputs are always fully written.
+ * dss_sample_mesh_surface: three kernels behind one memset -- per face len with the per-mesh maximum folded in (integer
+ * atomicMax on the bits of len >= 0); one workgroup per mesh for the keys and their scan; one thread per (n, s).  normals
+ * and bary may be NULL.  No float atomics, nothing is read back: capturable in a graph.  Workspace:
+ * dss_mesh_sample_workspace(N, F), known on the host (0 for sizes the entry refuses).
+ * dss_mesh_sample_backward: with face_idx and bary held constant, grad_verts[v] = the sum of bary[n,s,c] g_points[n,s,:]
+ * over the entries e = 3 (n S + s) + c whose corner c is vertex v, products and sums in fp32, added in ascending e.  order
+ * (3 N S,) = the entries sorted by (packed id of the vertex at that corner, e), entries of face_idx -1 or of a vertex id
+ * outside [0, V) last; one thread per vertex finds its segment by binary search, as dss_mesh_distance_backward does.  No
+ * atomics; grad_verts (V,3) is fully written; a repeated call returns the same bits.  Normals carry no gradient.
+ * Refusals (DSS_ERR_INVALID_ARGUMENT, nothing launched): N outside [1, 65535]; F, V outside [0, 2^31); S < 0 or
+ * N S > 2^38; a NULL tensor that would be read or written.  A short or NULL workspace is DSS_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+DSS_API size_t dss_mesh_sample_workspace(int N, int64_t F);
+DSS_API int dss_sample_mesh_surface(const float *verts /* (V,3) */, int64_t V, const int64_t *faces /* (F,3) */,
+                                    const int64_t *f_first, const int64_t *f_num, int64_t F, int N, int64_t S, uint64_t seed,
+                                    float *points /* (N,S,3) */, float *normals /* (N,S,3) or NULL */,
+                                    int64_t *face_idx /* (N,S) */, float *bary /* (N,S,3) or NULL */, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+DSS_API int dss_mesh_sample_backward(const int64_t *faces /* (F,3) */, const int64_t *f_first, const int64_t *f_num, int64_t F,
+                                     int N, int64_t S, int64_t V, const int64_t *face_idx /* (N,S) */,
+                                     const float *bary /* (N,S,3) */, const int64_t *order /* (3 N S,) */,
+                                     const float *g_points /* (N,S,3) */, float *grad_verts /* (V,3) */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * One round of sparsity upsampling: `upsample` of DSS/core/cloud.py:555-632 inserts points where a neighbourhood is
  * sparsest, a tenth of the cloud per round.  The reference materialises an (N,P,K,K,3) tensor; here one kernel searches the
  * K x K candidates of every point and a second one assembles the grown cloud.  Between them the caller sorts `key` (one
